@@ -10,7 +10,10 @@ Workloads (BASELINE.json configs):
                    independent 32 KiB streams (each == the reference's
                    snappy_compress() of its chunk), strong-scaled over the N
                    ranks (1 GiB global pieces, block-cyclic), so --gpus
-                   1/2/4/8 is one job on one curve.  At N = 1 the same JSON line carries
+                   1/2/4/8 is one job on one curve.  A plain run sets up, warms
+                   up, times --steps steps and prints the line.  With --full, at
+                   N = 1, the same JSON line also carries the CPU baselines, the
+                   measured HBM copy rate, host_end_to_end and
                    compact sub-results for the other configs -- text32k
                    (configs[1]: 1 GiB of the same streams), text64k (one
                    snappy_compress() stream of 64 KiB blocks), random +
@@ -35,7 +38,11 @@ stream; C2 and the decode overlap the next step's compress -- and reports it
 as `value_end_to_end`.  C3 (all-gather of the decoded shards) is opt-in
 (--c3).  Every phase is checked (round trip, per-piece checksums).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+--dump-outputs DIR writes what the last timed step computed (the compressed
+payload, its unit offsets, the decoded bytes; seeded samples of the large
+ones) as DIR/<name>.npy, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                        [--workload text32k|text64k|random|repeat|decode10g]
                        [--total-bytes T | --weak [--bytes-per-gpu B]]
 --gpus N without a torch.distributed launcher spawns the N ranks itself
@@ -95,6 +102,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the HBM copy rate and, at N = 1, the "
+                         "CPU baselines, the host API samples, the sub-results of the other configs, the FILE* API")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32 / float64, "
+                         "fixed seeded samples of the large ones)")
     ap.add_argument("--workload", default="text32k", choices=sorted(WORKLOADS))
     ap.add_argument("--bytes-per-gpu", type=int, default=None,
                     help="weak scaling: input bytes per rank (default 1 GiB with --weak)")
@@ -119,9 +132,9 @@ def parse(argv=None):
     ap.add_argument("--e2e-steps", type=int, default=3, help="N > 1: steps of the end-to-end loop")
     ap.add_argument("--overlap", action="store_true",
                     help="decode piece k on a second stream while piece k + 1 compresses")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-e2e", action="store_true", help="skip the PCIe-inclusive host API samples")
-    ap.add_argument("--no-sub", action="store_true", help="N = 1: skip the sub-results of the other configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-host-e2e", action="store_true", help="--full: skip the PCIe-inclusive host API samples")
+    ap.add_argument("--no-sub", action="store_true", help="--full: skip the sub-results of the other configs")
     ap.add_argument("--file-api-bytes", type=int, default=4 * GiB, help="host_file_api: size of the /dev/shm file")
     ap.add_argument("--keep-size", action="store_true", help="decode10g: use --bytes-per-gpu as given")
     ap.add_argument("--dist-world1", action="store_true",
@@ -132,7 +145,10 @@ def parse(argv=None):
     ap.add_argument("--pmc", default=None,
                     help="rocprofv3 PMC summary giving HBM traffic per launch (default: the profiles/pmc_*.json "
                          "written by tools/pmc_summary.py for this workload and launch size)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -440,6 +456,48 @@ def checksum(t: torch.Tensor) -> int:
     return s & ((1 << 62) - 1)
 
 
+DUMP_RUN = 4096  # --dump-outputs keeps a large output as runs of this many consecutive elements
+DUMP_BYTE_ELEMS = 4 << 20  # elements kept of the payload and of the decoded bytes (16 MiB each as float32)
+DUMP_OFFSET_ELEMS = 3 << 20  # unit offsets kept (24 MiB as float64: configs[3]'s 2,097,153 in full)
+
+
+def sample_runs(n: int, elems: int, seed: int):
+    """Which part of an n-element output --dump-outputs keeps: None (all of
+    it) when n <= elems, else the start offsets of elems // DUMP_RUN runs of
+    DUMP_RUN elements, one at a seeded position in each of as many equal
+    strata of the output.  The same (n, elems, seed) gives the same runs."""
+    if n <= elems:
+        return None
+    k = elems // DUMP_RUN
+    stride = n // k
+    rng = np.random.default_rng(seed)
+    return np.arange(k, dtype=np.int64) * stride + rng.integers(0, stride - DUMP_RUN + 1, size=k)
+
+
+def sampled(t: torch.Tensor, n: int, elems: int, seed: int, dtype) -> np.ndarray:
+    """t[:n] (or its sample_runs) as a host array of dtype."""
+    starts = sample_runs(n, elems, seed)
+    s = t[:n] if starts is None else torch.cat([t[o:o + DUMP_RUN] for o in starts.tolist()])
+    return s.cpu().numpy().astype(dtype)
+
+
+def dump_outputs(job, clen: int, dirname: str, suffix: str = "") -> None:
+    """--dump-outputs: what the last timed step left for its caller, as
+    DIR/<name><suffix>.npy -- `decompressed` (float32, the decoded bytes) and,
+    unless the workload only decodes, `compressed` (float32, the payload's
+    clen bytes) and `compressed_offsets` (float64, exact below 2^53: where
+    each unit starts in the payload, and clen).  At most 56 MiB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"decompressed": sampled(job.back, job.n, DUMP_BYTE_ELEMS, 1, np.float32)}
+    if not job.decode_only:
+        arrays["compressed"] = sampled(job.out, clen, DUMP_BYTE_ELEMS, 2, np.float32)
+        offs = torch.cat([p.offs[:-1] + p.out_off for p in job.pieces] +
+                         [torch.tensor([clen], dtype=torch.int64, device=job.dev)])
+        arrays["compressed_offsets"] = sampled(offs, offs.numel(), DUMP_OFFSET_ELEMS, 3, np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+
 def load_pmc(path, workload: str, n: int) -> dict:
     """{kernel: hbm_bytes per launch} from the tools/pmc_summary.py file
     measured on this workload with launches of n input bytes (the file at
@@ -508,13 +566,23 @@ class Job:
             xo += m
         # the rank's pieces in HBM, generated on the host 1 GiB at a time
         self.x = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        host = np.empty(min(max(n, 1), GiB), dtype=np.uint8)
+        # (a larger input through two pinned buffers: one fills while the other's copy is in flight)
+        host = [torch.empty(min(max(n, 1), GiB), dtype=torch.uint8, pin_memory=True) for _ in range(2 if n > GiB else 1)]
+        copied = [None] * len(host)
+        i = 0
         for gp in self.gpieces:
             for o in range(0, gp.n, GiB):
                 m = min(GiB, gp.n - o)
-                datagen.fill(host[:m], kind, seed, offset=gp.goff + o, threads=16)
-                self.x[gp.xoff + o:gp.xoff + o + m].copy_(torch.from_numpy(host[:m]))
-        del host
+                b = i % len(host)
+                if copied[b] is not None:
+                    copied[b].synchronize()
+                datagen.fill(host[b].numpy()[:m], kind, seed, offset=gp.goff + o, threads=16)
+                self.x[gp.xoff + o:gp.xoff + o + m].copy_(host[b][:m], non_blocking=True)
+                copied[b] = torch.cuda.Event()
+                copied[b].record()
+                i += 1
+        torch.cuda.synchronize(dev)
+        del host, copied
         self.units = codec.num_units(n, chunk, layout)
         # the timed loop's launches over x: x[0] is global offset 0 only on the rank owning piece 0
         first_global = bool(self.gpieces) and self.gpieces[0].goff == 0
@@ -841,6 +909,8 @@ def main():
     else:
         total_comp = clen
     mem_after_steps = torch.cuda.mem_get_info(dev)
+    if args.dump_outputs:
+        dump_outputs(job, clen, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     assemble = None
     if use_dist and not args.no_assemble and not decode_only:
@@ -867,12 +937,13 @@ def main():
 
     line = None
     if rank == 0:
-        hbm_gbps = hbm_copy_gbps(dev)
+        # a plain run stops at its headline figure; the legs that take runs of their own need --full
+        hbm_gbps = hbm_copy_gbps(dev) if args.full else None
         cpu = cpu_all = cpu_ref = e2e = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, cpu_all = cpu_baseline(kind, seed, chunk, layout, min(args.cpu_sample_bytes, n), decode_only)
             cpu_ref = cpu_reference(kind, seed, chunk, layout, min(128 << 20, n), decode_only)
-        if world == 1 and not args.no_host_e2e and not decode_only:
+        if args.full and world == 1 and not args.no_host_e2e and not decode_only:
             e2e = host_end_to_end(kind, seed, min(n, 256 << 20))
         size_txt = (f"{total_in / GiB:.4g} GiB in total over {world} GPU(s)" if strong else
                     f"{n / GiB:.4g} GiB/GPU")
@@ -915,7 +986,7 @@ def main():
         if assemble:
             line["value_end_to_end"] = assemble.pop("value_end_to_end")
             line["exchange"] = assemble
-    if rank == 0 and world == 1 and not args.no_sub and config3:
+    if args.full and rank == 0 and world == 1 and not args.no_sub and config3:
         subs = {}
         sub_steps, sub_warm = max(1, min(args.steps, 10)), min(args.warmup, 2)
         for w in SUB_WORKLOADS:

@@ -101,3 +101,73 @@ def test_e2e_piece_larger_than_job_is_the_job():
     big = sdist.rank_plan(total, 1, 32768, 8 * GiB, e2e_piece=4 * GiB)
     same = sdist.rank_plan(total, 1, 32768, 8 * GiB, e2e_piece=e2e)
     assert big == same
+
+
+def test_dump_sample_is_fixed_and_in_bounds():
+    """--dump-outputs: an output within the budget is kept whole; a larger one
+    as the same seeded runs every time, one per stratum, all inside it."""
+    assert bench.sample_runs(bench.DUMP_BYTE_ELEMS, bench.DUMP_BYTE_ELEMS, 1) is None
+    for n in (bench.DUMP_BYTE_ELEMS + 1, 64 * GiB, 38_000_000_001):
+        s = bench.sample_runs(n, bench.DUMP_BYTE_ELEMS, 1)
+        assert len(s) * bench.DUMP_RUN == bench.DUMP_BYTE_ELEMS
+        assert s[0] >= 0 and s[-1] + bench.DUMP_RUN <= n and (s[1:] - s[:-1] >= bench.DUMP_RUN).all()
+        assert (s == bench.sample_runs(n, bench.DUMP_BYTE_ELEMS, 1)).all()
+    # the three arrays of one dump stay under 64 MB
+    assert 4 * 2 * bench.DUMP_BYTE_ELEMS + 8 * bench.DUMP_OFFSET_ELEMS + 3 * 128 < 64_000_000
+
+
+def test_dump_outputs_arrays(tmp_path):
+    """dump_outputs on host tensors: the payload's clen bytes, the units'
+    global offsets over two launches and the decoded bytes, as float32 /
+    float64 .npy files; a large output comes out as its sampled runs."""
+    import types
+
+    import numpy as np
+    import torch
+    n = bench.DUMP_BYTE_ELEMS + 12345
+    back = (torch.arange(n, dtype=torch.int64) % 251).to(torch.uint8)
+    out = torch.arange(100, dtype=torch.uint8)
+    pieces = [types.SimpleNamespace(offs=torch.tensor([0, 10, 30]), out_off=0),
+              types.SimpleNamespace(offs=torch.tensor([0, 20, 45]), out_off=30)]
+    job = types.SimpleNamespace(back=back, n=n, out=out, pieces=pieces, decode_only=False, dev="cpu")
+    bench.dump_outputs(job, 75, str(tmp_path))
+    comp = np.load(tmp_path / "compressed.npy")
+    offs = np.load(tmp_path / "compressed_offsets.npy")
+    dec = np.load(tmp_path / "decompressed.npy")
+    assert comp.dtype == np.float32 and comp.tolist() == list(range(75))
+    assert offs.dtype == np.float64 and offs.tolist() == [0, 10, 30, 50, 75]
+    starts = bench.sample_runs(n, bench.DUMP_BYTE_ELEMS, 1)
+    want = np.concatenate([back[o:o + bench.DUMP_RUN].numpy() for o in starts])
+    assert dec.dtype == np.float32 and dec.size == bench.DUMP_BYTE_ELEMS and np.array_equal(dec, want)
+    job.decode_only = True  # a decode-only workload returns the decoded bytes alone
+    bench.dump_outputs(job, 75, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["decompressed.npy"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) of a small job: the line carries the headline
+    keys and none of the --full legs, and --dump-outputs writes the last
+    step's outputs -- the oracle's streams of the same seeded input, their
+    offsets, and the input back."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    import datagen
+    import oracle
+    n = 5 * 32768 + 777
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--bytes-per-gpu", str(n), "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["round_trip_ok"] and d["dtype"] == "u8"
+    assert d["unit"] == "MB/s" and d["higher_is_better"] is True and d["value"] > 0
+    assert d["cpu_baseline"] is None and d["host_end_to_end"] is None and "configs" not in d
+    a = datagen.make("T", n, 1234)
+    want, want_offs = oracle.compress_streams(a, 32768)
+    assert np.array_equal(np.load(tmp_path / "compressed.npy"), want.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "compressed_offsets.npy"), np.asarray(want_offs, dtype=np.float64))
+    assert np.array_equal(np.load(tmp_path / "decompressed.npy"), a.astype(np.float32))

@@ -19,10 +19,10 @@ for step in "$@"; do
         rc=$?; echo "tests rc=$rc"; tail -3 "$out/gpu_tests.log"
         fatal $rc && exit $rc ;;
     bench)
-        timeout -k 10 500 python -u bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+        timeout -k 10 500 python -u bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
         rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && exit $rc ;;
     n1_64g)  # the N = 1 point of configs[3]: 64 GiB of 32 KiB text streams on one GPU
-        timeout -k 10 600 python -u bench.py --total-bytes 68719476736 --steps 5 --warmup 1 \
+        timeout -k 10 600 python -u bench.py --full --total-bytes 68719476736 --steps 5 --warmup 1 \
             --cpu-sample-bytes 268435456 > "$out/n1_64g.json" 2> "$out/n1_64g.err"
         rc=$?; echo "n1_64g rc=$rc"; [ $rc -ne 0 ] && exit $rc ;;
     prof64g)
@@ -104,17 +104,17 @@ for step in "$@"; do
         rc=$?; echo "copypath rc=$rc"; cat "$out/copy_path.log"; [ $rc -ne 0 ] && exit $rc ;;
     hostinbench)  # the bench line's host_end_to_end after a 1 GiB and after the 64 GiB job (no sub-results, no CPU baselines)
         for tb in 1073741824 68719476736; do
-            timeout -k 10 400 python -u bench.py --total-bytes $tb --steps 2 --warmup 1 --no-sub --no-cpu-baseline \
+            timeout -k 10 400 python -u bench.py --full --total-bytes $tb --steps 2 --warmup 1 --no-sub --no-cpu-baseline \
                 > "$out/hostinbench_$tb.json" 2> "$out/hostinbench_$tb.err"
             rc=$?; echo "hostinbench $tb rc=$rc: $(python3 -c "import json,sys; print(json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])['host_end_to_end'])" "$out/hostinbench_$tb.json")"
             [ $rc -ne 0 ] && exit $rc
         done
         timeout -k 10 500 rocprofv3 --kernel-trace --memory-copy-trace -d "$out/hostinbench_trace" -o run --output-format csv -- \
-            python3 bench.py --steps 1 --warmup 1 --no-sub --no-cpu-baseline > "$out/hostinbench_trace.log" 2>&1
+            python3 bench.py --full --steps 1 --warmup 1 --no-sub --no-cpu-baseline > "$out/hostinbench_trace.log" 2>&1
         rc=$?; echo "hostinbench trace rc=$rc"; [ $rc -ne 0 ] && exit $rc ;;
     hostenv)  # host_end_to_end inside a 1 GiB bench run: as is, with high-priority lane streams, with 8 hardware queues
         for e in ${HOSTENV_SET:-"X=1" "SNAPPY_AMD_PIPE_PRIO=1" "GPU_MAX_HW_QUEUES=8"}; do
-            env $e timeout -k 10 300 python -u bench.py --total-bytes 1073741824 --steps 2 --warmup 1 --no-sub --no-cpu-baseline \
+            env $e timeout -k 10 300 python -u bench.py --full --total-bytes 1073741824 --steps 2 --warmup 1 --no-sub --no-cpu-baseline \
                 > "$out/hostenv_$e.json" 2> "$out/hostenv_$e.err"
             rc=$?; echo "hostenv $e rc=$rc: $(python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(d['value'], d['host_end_to_end'])" "$out/hostenv_$e.json")"
             [ $rc -ne 0 ] && exit $rc

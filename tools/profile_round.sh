@@ -30,7 +30,7 @@ run() {  # workload
     local q="$sel --no-cpu-baseline --no-host-e2e --no-sub"
     mkdir -p $d &&
     echo "[$(date +%T)] $w: bench" &&
-    timeout -k 10 400 python3 bench.py $sel --steps $STEPS --warmup 2 --cpu-sample-bytes 268435456 --no-sub \
+    timeout -k 10 400 python3 bench.py $sel --full --steps $STEPS --warmup 2 --cpu-sample-bytes 268435456 --no-sub \
         > $d/bench.json 2> $d/bench.err &&
     echo "[$(date +%T)] $w: kernel trace" &&
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $d/trace -o run --output-format csv -- \
