@@ -240,17 +240,28 @@ __device__ __forceinline__ uint32_t funnel_bytes(uint32_t hi, uint32_t lo, uint3
     return __builtin_amdgcn_perm(hi, lo, sel);
 }
 
-// bit d (1 <= d <= D) set iff lane l - d carries the same x as lane l (x != 0)
+// The nearest lane l - d (1 <= d <= D) whose word has the same upper half as
+// the lane's own w, as d << 8 | that lane's low byte; >= 65536 if there is none.
+// w = key << 16 | tag with key >= 1 and tag < 256: the word shifted d lanes up
+// has gained d << 8 (no carry into the key for D <= 16), its xor with the own
+// key << 16 is below 65536 exactly where the keys agree, and the minimum over d
+// is the nearest such lane with its tag.  Lanes without a source shift in 0, a
+// key no lane has.  One DPP add, one xor and half a min3 per distance.
 template <uint32_t D>
-__device__ __forceinline__ uint32_t same_x_bits(uint32_t x)
+__device__ __forceinline__ uint32_t nearest_same_key(uint32_t w)
 {
-    uint32_t xs = x, bits = 0;
+    static_assert(D <= 16, "d << 8 must stay below the key");
+    const uint32_t x0 = w & 0xFFFF0000u;
+    uint32_t xs = w, best = 0xFFFFFFFFu, k100;
+    // 0x100 in a VGPR the compiler cannot fold back into a literal: a DPP add takes
+    // none, so with a literal the shift stays a v_mov_b32_dpp of its own
+    asm("v_mov_b32 %0, 0x100" : "=v"(k100));
 #pragma unroll
     for (uint32_t d = 1; d <= D; d++) {
-        xs = wave_shr1(xs);
-        bits |= (xs == x) ? (1u << d) : 0u;
+        xs = wave_shr1(xs) + k100;
+        best = __builtin_elementwise_min(best, xs ^ x0);
     }
-    return bits;
+    return best;
 }
 
 __device__ __forceinline__ uint32_t varint_len(uint64_t v)
@@ -314,11 +325,15 @@ __device__ __forceinline__ uint32_t tconf(uint32_t h, uint32_t a, uint32_t notdu
                             // measured, profiles/r03h_ab_k1r_dmax_rmin_*; with the round-5 asm loop at
                             // its best loop placement 8 / 9 / 10: 12.46 / 12.37 / 12.23 ms per GiB,
                             // profiles/r05zw_*; round 6 at RMIN 2: 11 / 13 / 14 / 16 -> 12.31-12.32 /
-                            // 12.26-12.27 / 12.34-12.37 / 12.52-12.58, profiles/r06m_*)
+                            // 12.26-12.27 / 12.34-12.37 / 12.52-12.58, profiles/r06m_*; with the
+                            // min-reduction search 12 / 13 / 14 -> 11.92-11.96 / 11.88-11.90 /
+                            // 11.89-11.91, profiles/r07a_*)
 #endif
 #ifndef SNAPPY_K1R_DMAX64
 #define SNAPPY_K1R_DMAX64 12  // K1r64 (65,536-byte blocks): round 6 at RMIN 2, 10 / 12 / 13 / 14 ->
-                              // 14.07-14.09 / 14.03-14.04 / 14.42 / 14.12-14.13 ms per GiB (r06m_*)
+                              // 14.07-14.09 / 14.03-14.04 / 14.42 / 14.12-14.13 ms per GiB (r06m_*);
+                              // with the min-reduction search 11 / 12 / 13 -> 13.18-13.21 /
+                              // 13.15-13.18 / 13.27-13.28 (r07a_*)
 #endif
 #ifndef SNAPPY_K1R_LSMIN
 #define SNAPPY_K1R_LSMIN 4  // lane-space rounds while at least this many step-1 probes remain
@@ -693,14 +708,14 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
         WINDOW_AT(qq);                                                                             \
         adr = TBL_ADR(hv & 0xFFFF);                                                                \
         TBL_READ_ENT(adr); /* in flight during the lane data below */                             \
-        const uint32_t _bits = same_x_bits<DMAX>((hv & 0xFFFF) + 1);                               \
-        const uint32_t _pd = _bits ? (uint32_t)__builtin_ctz(_bits) : 0u;                          \
+        /* the nearest same-hash lane within DMAX before this one, and its tag */                  \
+        const uint32_t _best = nearest_same_key<DMAX>(__builtin_amdgcn_alignbit(hv, hv, 16) + 0x10000u); \
+        const bool _has = _best < 65536u;                                                          \
+        const uint32_t _pd = _has ? _best >> 8 : 0u;                                               \
         /* lane - pd + 1, or lane - 1 at pd = 1: pdl1 >= lane0 also implies lane > lane0 */      \
-        pdl1 = _bits ? lane - _pd + 1 - (_pd == 1 ? 1u : 0u) : 0xFFFFFF00u; /* signed: below every lane0 */ \
+        pdl1 = _has ? lane - _pd + 1 - (_pd == 1 ? 1u : 0u) : 0xFFFFFF00u; /* signed: below every lane0 */ \
         pdc = q0 + lane - _pd;                                                                     \
-        const uint32_t _hp = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane - _pd) << 2), (int)hv); \
-        /* the predecessor's tag */                                                                \
-        pdnz = (_hp >> 16) & 0xFFu;                                                                \
+        pdnz = _best & 0xFFu; /* (read only where pdl1 says there is a predecessor) */             \
         /* probe lanes: <= 62 and not past is_block_end (L - p >= 16, 17 at skip 64) */           \
         const int32_t _w16 = (int32_t)(L - 16 - q0), _w17 = (int32_t)(L - 17 - q0);              \
         const bool _inw = (int32_t)lane <= _w16 && lane <= 62;                                     \
@@ -884,7 +899,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #define K1R_HIT32 K1R_HIT_PREDTAG
 #define K1R_HIT64 K1R_HIT_PREDTAG
 #define K1R_DRAIN                                                                                   \
-    K1R_DRAIN_PACK                                                                                  \
     "s_mov_b32 m0, %[pend]\n\t" /* (gfx950 refuses two SGPRs in a v_writelane: m0 stays) */          \
     "v_writelane_b32 %[tka], %[dka], m0\n\t"                                                        \
     "v_writelane_b32 %[tkb], %[dkb], m0\n\t"                                                        \
@@ -909,39 +923,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #ifndef SNAPPY_K1R_X45
 #define SNAPPY_K1R_X45 1
 #endif
-// SNAPPY_K1R_PACK_DRAIN: a hit round leaves its token as pf (dka) and the length
-// (dlen, the read-back's own register) and the next round's drain packs them
-// (one s_pack in the drain, one s_mov of pf in the gather wait's shadow) instead
-// of an s_pack on the tail after the length read-back; every exit that keeps a
-// token pending packs it itself (the leaving path) or hands it to C++ (codes 4/5).
-// Slower at every loop placement (A/B, outputs identical, 68 GPU tests green,
-// profiles/r06aj_*: K1r 12.04 -> 12.18 at best, K1r64 13.49-13.51 -> 13.67 at
-// best: the pack now sits on the next round's drain before its writelanes), so off
-#ifndef SNAPPY_K1R_PACK_DRAIN
-#define SNAPPY_K1R_PACK_DRAIN 0
-#endif
-#if SNAPPY_K1R_PACK_DRAIN
-#define K1R_LEN "%[dlen]"
-#define K1R_DRAIN_PACK "s_pack_ll_b32_b16 %[dka], %[dka], %[dlen]\n\t"
-#define K1R_DKA_SHADOW "s_mov_b32 %[dka], %[pf]\n\t"
-#define K1R_DKA_TAIL
-#define K1R_DLEN_DECL uint32_t _dlen = dka >> 16; /* the pending token's length */
-#define K1R_DLEN_OP [dlen] "+s"(_dlen),
-#else
-#define K1R_LEN "%[s0]"
-#define K1R_DRAIN_PACK
-#define K1R_DKA_SHADOW
-#define K1R_DKA_TAIL "s_pack_ll_b32_b16 %[dka], %[pf], %[s0]\n\t"
-#define K1R_DLEN_DECL
-#define K1R_DLEN_OP
-#endif
 #if SNAPPY_K1R_X45
 #define K1R_LENCHECK                                                                                \
-    "v_readlane_b32 " K1R_LEN ", %[t2], %[s1]\n\t"                                                 \
-    "s_add_u32 %[s2], " K1R_LEN ", -4\n\t"                                                          \
+    "v_readlane_b32 %[s0], %[t2], %[s1]\n\t"                                                        \
+    "s_add_u32 %[s2], %[s0], -4\n\t"                                                                \
     "s_cmp_gt_u32 %[s2], 59\n\t"                                                                    \
     "s_cbranch_scc1 L%=_x4\n\t"
-#define K1R_X4 "s_cmp_lt_u32 " K1R_LEN ", 4\n\ts_cbranch_scc1 L%=_x5\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n"
+#define K1R_X4 "s_cmp_lt_u32 %[s0], 4\n\ts_cbranch_scc1 L%=_x5\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n"
 #else
 #define K1R_LENCHECK                                                                                \
     "s_cmp_gt_u32 %[s1], 15\n\t"                                                                    \
@@ -951,52 +939,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_cbranch_scc1 L%=_x5\n\t"
 #define K1R_X4 "s_mov_b32 %[code], 4\n\ts_branch L%=_end\n"
 #endif
-// SNAPPY_K1R_EARLY_INS: a hit round's inserts and next entry reads issued as
-// soon as the insert range is known, before the wait for the gathers, which
-// then waits for pa and ca alone (lgkmcnt(4): one wave's LDS operations
-// complete in order; the K1r64 far path's ca is a global load, so there the
-// count leaves pa's four successors); 0: after the funnels (round 5's V18).
-// Measured slower at every loop placement (A/B, outputs identical, 68 GPU tests
-// green on it, profiles/r06z_*: K1r 12.09-12.12 -> 12.18 at best, 12.26-12.59
-// elsewhere; K1r64 equal), so off
-#ifndef SNAPPY_K1R_EARLY_INS
-#define SNAPPY_K1R_EARLY_INS 0
-#endif
-#if SNAPPY_K1R_EARLY_INS
-#define K1R_INS_EARLY K1R_INSERTS("%[s2]", "%[s0]")
-#define K1R_INS_LATE
-#define K1R_GATHER_WAIT "s_waitcnt lgkmcnt(4)\n\t" /* pa and ca; the inserts and entry reads stay in flight */
-#else
-#define K1R_INS_EARLY
-#define K1R_INS_LATE K1R_INSERTS("%[s2]", "%[s0]")
-#define K1R_GATHER_WAIT "s_waitcnt lgkmcnt(0)\n\t" /* pa and ca */
-#endif
-// the miss round's way on: SNAPPY_K1R_NOHIT2 tests the common case first --
-// lane0 <= lim0 = min(62 - RMIN, L - 16 - q0) (window and block end in one
-// signed compare, as the hit path) and skip <= skipmax -- and tells the rare
-// ends apart after it; 0: the four tests in turn.  Two compares and two branches
-// fewer per miss round, yet slower at every loop placement (A/B, outputs
-// identical, profiles/r06ae_*: K1r 12.10-12.13 -> 12.16-12.45 ms per GiB, K1r64
-// 13.57 -> 13.58-13.69), so off
-#ifndef SNAPPY_K1R_NOHIT2
-#define SNAPPY_K1R_NOHIT2 0
-#endif
-#if SNAPPY_K1R_NOHIT2
-#define K1R_NOHIT_TAIL(T)                                                                           \
-    "s_cmp_le_i32 %[lane0], %[lim0]\n\t"                                                           \
-    "s_cbranch_scc0 L%=_nx" T "\n\t"                                                              \
-    "s_cmp_le_u32 %[skip], %[skipmax]\n\t"                                                         \
-    "s_cbranch_scc1 L%=_top" T "\n\t"                                                             \
-    "s_cmp_gt_u32 %[skip], %[lsmax]\n\t"                                                           \
-    "s_cbranch_scc1 L%=_x1\n\t"                                                                    \
-    "s_branch L%=_x3\n"                                                                            \
-    "L%=_nx" T ":\n\t"                                                                            \
-    "s_cmp_gt_u32 %[skip], %[lsmax]\n\t"                                                           \
-    "s_cbranch_scc1 L%=_x1\n\t"                                                                    \
-    "s_cmp_gt_u32 %[p], %[lm16]\n\t"                                                               \
-    "s_cbranch_scc1 L%=_x1\n\t"                                                                    \
-    "s_branch L%=_x2\n"
-#else
+// the miss round's way on: the four tests in turn
 #define K1R_NOHIT_TAIL(T)                                                                           \
     "s_cmp_gt_u32 %[skip], %[lsmax]\n\t"                                                           \
     "s_cbranch_scc1 L%=_x1\n\t"                                                                    \
@@ -1006,7 +949,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_cbranch_scc1 L%=_x2\n\t"                                                                    \
     "s_cmp_le_u32 %[skip], %[skipmax]\n\t"                                                         \
     "s_cbranch_scc1 L%=_top" T "\n"
-#endif
 // SNAPPY_K1R_EARLY_DK: a hit round's token offset written right after the drain
 // that consumed the previous one (in the gather wait's shadow) instead of on the
 // tail after the length read-back.  (The pending flag stays on the tail: the
@@ -1048,22 +990,20 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "L%=_farret" T ":\n\t"                                                                       \
             K1R_DRAIN /* the previous round's token, during the gathers */                         \
             K1R_DK_EARLY                                                                            \
-            K1R_DKA_SHADOW                                                                          \
             "s_cmp_lt_u32 %[lane0], %[f]\n\t"                                                       \
             "s_subb_u32 %[s0], %[lane0], 0\n\t" /* lo0 */                                           \
             "v_mul_i32_i24_e64 %[t0], %[pf], -8\n\t" /* pa's funnel shift */                        \
             "s_sub_u32 %[s2], %[f], %[s0]\n\t"                                                      \
             "s_add_u32 %[s2], %[s2], 1\n\t" /* lanes lo0 .. f insert */                             \
-            K1R_INS_EARLY                                                                           \
             "s_and_b32 %[s3], %[c], 3\n\t"                                                          \
             "s_mul_i32 %[s3], %[s3], 0xfefefeff\n\t"                                                \
             "s_add_i32 %[s3], %[s3], 0x7060504\n\t" /* ca's perm selector */                        \
-            K1R_GATHER_WAIT                                                                         \
+            "s_waitcnt lgkmcnt(0)\n\t" /* pa and ca */                                               \
             "v_mov_b32_dpp %[t1], %[t2] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"     \
             "v_mov_b32_dpp %[t4], %[t3] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"     \
             "v_alignbit_b32 %[t2], %[t2], %[t1], %[t0]\n\t"                                         \
             "v_perm_b32 %[t3], %[t3], %[t4], %[s3]\n\t"                                             \
-            K1R_INS_LATE                                                                            \
+            K1R_INSERTS("%[s2]", "%[s0]")                                                           \
             "v_cmp_ne_u32_e32 vcc, %[t2], %[t3]\n\t"                                                \
             "v_xor_b32_e32 %[t2], %[t2], %[t3]\n\t"                                                 \
             "v_ffbh_u32_e32 %[t2], %[t2]\n\t"                                                       \
@@ -1071,16 +1011,16 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "v_lshl_or_b32 %[t2], %[lane], 2, %[t2]\n\t" /* the prefix length if this dword differs */ \
             "s_ff1_i32_b32 %[s1], vcc_lo\n\t"                                                       \
             K1R_LENCHECK                                                                            \
-            "s_add_u32 %[lane0], %[f], " K1R_LEN "\n\t"                                             \
-            K1R_DKA_TAIL                                                                            \
+            "s_add_u32 %[lane0], %[f], %[s0]\n\t"                                                   \
+            "s_pack_ll_b32_b16 %[dka], %[pf], %[s0]\n\t"                                           \
             K1R_DK_LATE                                                                             \
             "s_cmp_le_i32 %[lane0], %[lim0]\n\t" /* implies pf + len <= L - 16: no clamp */         \
             "s_cbranch_scc1 L%=_top" T "\n\t"                                                            \
             "s_sub_u32 %[s2], %[L], %[pf]\n\t" /* leaving: the length clamped to the block end */ \
-            "s_min_u32 " K1R_LEN ", " K1R_LEN ", %[s2]\n\t"                                          \
-            "s_add_u32 %[p], %[pf], " K1R_LEN "\n\t"                                                \
+            "s_min_u32 %[s0], %[s0], %[s2]\n\t"                                                     \
+            "s_add_u32 %[p], %[pf], %[s0]\n\t"                                                      \
             "s_sub_u32 %[lane0], %[p], %[q0]\n\t"                                                   \
-            "s_lshl_b32 %[s1], " K1R_LEN ", 16\n\t"                                                 \
+            "s_lshl_b32 %[s1], %[s0], 16\n\t"                                                       \
             "s_or_b32 %[dka], %[s1], %[pf]\n\t"                                                     \
             "s_cmp_gt_u32 %[p], %[lm16]\n\t"                                                        \
             "s_cbranch_scc1 L%=_x1\n\t"                                                             \
@@ -1122,7 +1062,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP)    \
     do {                                                                                            \
         uint32_t _m0s, _pf, _s0, _s1, _s2, _s3, _t0, _t1, _t2, _t3, _t4;                            \
-        K1R_DLEN_DECL                                                                               \
         uint64_t _valid, _hm;                                                                       \
         asm volatile(                                                                               \
             "s_mov_b32 %[m0s], m0\n\t"                                                              \
@@ -1158,7 +1097,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "s_mov_b32 m0, %[m0s]\n\t"                                                              \
             "s_waitcnt lgkmcnt(0)"                                                                  \
             : [p] "+s"(p), [skip] "+s"(skip), [lane0] "+s"(lane0), [pend] "+s"(pend), [dka] "+s"(dka), \
-              [dkb] "+s"(dkb), [dkn] "+s"(dkn), K1R_DLEN_OP [code] "=&s"(code), [f] "=&s"(fx),         \
+              [dkb] "+s"(dkb), [dkn] "+s"(dkn), [code] "=&s"(code), [f] "=&s"(fx),                     \
               [c] "=&s"(cx),                                                                        \
               [m0s] "=&s"(_m0s), [pf] "=&s"(_pf), [s0] "=&s"(_s0), [s1] "=&s"(_s1), [s2] "=&s"(_s2),   \
               [s3] "=&s"(_s3), [valid] "=&s"(_valid), [hm] "=&s"(_hm), [ent] "+v"(e32),                \
