@@ -786,6 +786,11 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     const uint64_t t_loop = clock64();
     uint64_t rs_flush = 0, rs_win = 0, rs_asm = 0;
     uint32_t rs_n = 0, rs_nfl = 0, rs_nasm = 0, rs_code[6] = {0, 0, 0, 0, 0, 0};
+    // the glue around a code-2 refresh without a token flush: from the asm statement's
+    // end to the start of the window move, and from the refresh's end to the statement
+    uint64_t rs_gout = 0, rs_gin = 0, rs_ra1 = 0, rs_r2 = 0;
+    uint32_t rs_ng = 0;
+    bool rs_c2 = false, rs_gopen = false;
 #endif
 #ifdef SNAPPY_K1R_STATS
     const uint64_t t_loop = clock64();
@@ -800,7 +805,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     // entries read while the verification runs, the match length from the
     // first differing byte; a round without a hit inserts its nk probes.  It
     // leaves the loop with `code`: 1 = skip past the step-1 range or
-    // is_block_end, 2 = the window must move (refresh), 3 = the next round's
+    // is_block_end, 2 = the window must move (K1r64; K1r moves it inside the
+    // statement, K1R_WIN_PATH, and leaves only when a token flush is due), 3 = the next round's
     // probes reach a step of 2 (skip > 64 - DMAX: the C++ round), and mid-round
     // (inserts done, entries read) 4 = 64 or more equal bytes (C++ extends the
     // match), 5 = a tag collision (C++ finishes the miss).  Everything the
@@ -865,8 +871,10 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // r06n_*): PAD32 0..15 -> 12.18 (2) to 12.79 (13) ms per GiB; PAD64 -1 13.93,
 // 0..14 even 14.00-14.55.  With SNAPPY_K1R_X45 (r06x_*): PAD32 0 best (12.13-12.20;
 // 12.20-12.53 elsewhere), PAD64 -1 best (13.85-13.88; 13.92-14.53 pinned).
+// With the window refresh inside K1r's statement (profiles/r08b_*): PAD32 0..15 ->
+// 11.12-11.14 (2 and 10) to 11.46-11.49 (15) ms per GiB, the parent 11.91-11.92.
 #ifndef SNAPPY_K1R_PAD32
-#define SNAPPY_K1R_PAD32 2  // with SNAPPY_K1R_EARLY_DK (profiles/r06ag_*, r06ah_*)
+#define SNAPPY_K1R_PAD32 2  // with SNAPPY_K1R_WIN_INLOOP (profiles/r08b_*)
 #endif
 #ifndef SNAPPY_K1R_PAD64
 #define SNAPPY_K1R_PAD64 0  // with SNAPPY_K1R64_HALF32 (profiles/r06aa_*, r06ad_*)
@@ -946,7 +954,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_cmp_gt_u32 %[p], %[lm16]\n\t"                                                               \
     "s_cbranch_scc1 L%=_x1\n\t"                                                                    \
     "s_cmp_gt_u32 %[lane0], %[l0max]\n\t"                                                          \
-    "s_cbranch_scc1 L%=_x2\n\t"                                                                    \
+    "s_cbranch_scc1 L%=_win\n\t"                                                                    \
     "s_cmp_le_u32 %[skip], %[skipmax]\n\t"                                                         \
     "s_cbranch_scc1 L%=_top" T "\n"
 // SNAPPY_K1R_EARLY_DK: a hit round's token offset written right after the drain
@@ -1024,7 +1032,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "s_or_b32 %[dka], %[s1], %[pf]\n\t"                                                     \
             "s_cmp_gt_u32 %[p], %[lm16]\n\t"                                                        \
             "s_cbranch_scc1 L%=_x1\n\t"                                                             \
-            "s_branch L%=_x2\n"                                                                     \
+            "s_branch L%=_win\n"                                                                    \
             "L%=_nohit" T ":\n\t"                                                                        \
             K1R_SKIPFIX                                                                             \
             "s_and_b64 %[valid], %[valid], %[mwin]\n\t"                                             \
@@ -1059,7 +1067,120 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #define K1R64_HALF_SEL ""
 #define K1R64_HALF_LOOP ""
 #endif
-#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP)    \
+// SNAPPY_K1R_WIN_INLOOP: K1r's window refresh as a path of the statement (_win)
+// instead of a code-2 exit, the C++ WINDOW_LS and a re-entry, when no token
+// flush is due (pend + dkn <= 48: 444 of a 32 KiB text unit's 518 refreshes).
+// It is WINDOW_LS(p - 1) for !BIG with SNAPPY_K1R_WIN_ALIGN, instruction for
+// instruction the compiler's own schedule of it: the register pair of q0 / 256
+// under s_set_gpr_idx_on, two ds_bpermute and v_alignbit for each lane's BE32,
+// the kMul hash with its tag, the new entries read as soon as their addresses
+// exist, nearest_same_key<13> (every DPP read two states behind the VALU write
+// of its source), the lane data, word with bit 24 on the lanes past the window,
+// m_win and lim0; then lane0 = 1 and the skip test the statement's entry makes.
+// t0 = w, t1 = the shifted words, t2 = q0 + lane; pdl1 holds 0x100 and pdc a
+// distance's xor until the lane data are written; s0 = 0xFFFF0000.  VCC and an
+// SGPR pair written by VALU are read by VALU two or more instructions later.
+// m0: s_set_gpr_idx_on leaves the index there; every way on sets m0 before a
+// read (K1R_DRAIN, or the restore at _end), as after the candidate's gather.
+// exec is sx on entry (both tails restore it after their inserts) and is not
+// changed.  The stale entry reads of the old window land before the new ones
+// (LDS returns in order).  K1r64's refresh also moves the ring and waits for
+// its LDS-DMA segment: it has no such path (K1R_WIN_NONE: _win is _x2) and its
+// statement's operands are unchanged (its code is the parent's, instruction for
+// instruction).  A/B on 1 GiB of 32 KiB text streams, outputs identical, at all
+// 16 loop placements (profiles/r08b_*): 11.91-11.93 ms -> 11.13 at the pinned
+// placement; a unit enters the statement 111 times instead of 549 (r08a_*).
+// SNAPPY_K1R_WIN_INLOOP 0 is the parent's flow (every refresh by exit), kept for
+// the stamped measurement of that flow's glue and as the A/B control.
+#ifndef SNAPPY_K1R_WIN_INLOOP
+#define SNAPPY_K1R_WIN_INLOOP 1
+#endif
+#define K1R_WIN_NONE "L%=_win:\n"
+#define K1R_WIN_STEP(dst)                                                                           \
+    "v_add_u32_dpp %[t1], %[t1], %[pdl1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
+    "v_bitop3_b32 " dst ", %[t0], %[t1], %[s0] bitop3:0x6c\n\t" /* shifted ^ (w & 0xFFFF0000) */
+#define K1R_WIN_PAIR                                                                                \
+    K1R_WIN_STEP("%[t4]")                                                                           \
+    "s_nop 0\n\t"                                                                                   \
+    K1R_WIN_STEP("%[pdc]")                                                                          \
+    "v_min3_u32 %[pdnz], %[pdnz], %[t4], %[pdc]\n\t"
+#define K1R_WIN_PATH                                                                                \
+    "L%=_win:\n\t"                                                                                  \
+    K1R_SKIPFIX                                                                                     \
+    "s_add_u32 %[s0], %[pend], %[dkn]\n\t"                                                          \
+    "s_cmp_gt_u32 %[s0], 48\n\t" /* a token flush is due: the C++ refresh */                        \
+    "s_cbranch_scc1 L%=_x2\n\t"                                                                     \
+    "s_add_u32 %[q0], %[p], -1\n\t"                                                                 \
+    "s_lshr_b32 %[s0], %[q0], 8\n\t"                                                                \
+    "s_bfe_u32 %[s1], %[q0], 0x60002\n\t" /* dr */                                                  \
+    "s_set_gpr_idx_on %[s0], gpr_idx(SRC0)\n\t"                                                     \
+    "v_mov_b32_e32 %[t0], v2\n\t"                                                                   \
+    "v_mov_b32_e32 %[t1], v3\n\t"                                                                   \
+    "s_set_gpr_idx_off\n\t"                                                                         \
+    "v_cmp_gt_u32_e32 vcc, %[s1], %[lane]\n\t" /* lanes < dr take register R + 1 */                 \
+    "v_add_u32_e32 %[t2], %[q0], %[lane]\n\t"                                                       \
+    "v_mul_i32_i24_e64 %[t3], %[t2], -8\n\t" /* the funnel shift, as pa's */                        \
+    "v_add_u32_e32 %[t4], -1, %[t2]\n\t"                                                            \
+    "v_cndmask_b32_e32 %[dv], %[t0], %[t1], vcc\n\t"                                                \
+    "v_and_b32_e32 %[t4], -4, %[t4]\n\t" /* dwords from (p - 1) / 4 */                              \
+    "ds_bpermute_b32 %[t0], %[t4], %[dv]\n\t"                                                       \
+    "ds_bpermute_b32 %[t1], %[t4], %[dv] offset:4\n\t"                                              \
+    "s_mov_b32 %[s0], 0xffff0000\n\t"                                                               \
+    "s_mov_b32 %[s2], 0xff0000\n\t"                                                                 \
+    "s_sub_i32 %[s1], %[lm16], %[q0]\n\t" /* L - 16 - q0 */                                         \
+    "s_min_i32 %[lim0], %[s1], %[l0max]\n\t"                                                        \
+    "s_min_i32 %[s1], %[s1], 62\n\t" /* the last probe lane */                                      \
+    "s_mov_b32 %[lane0], 1\n\t"                                                                     \
+    "v_mov_b32_e32 %[pdl1], 0x100\n\t"                                                              \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                      \
+    "v_alignbit_b32 %[t0], %[t0], %[t1], %[t3]\n\t" /* BE32 at q0 + lane */                         \
+    "v_mul_lo_u32 %[t0], %[t0], %[kmul]\n\t"                                                        \
+    "v_lshrrev_b32_e32 %[adrt], %[shift], %[t0]\n\t" /* the slot */                                 \
+    "v_bfe_u32 %[t3], %[t0], %[sh8], 8\n\t" /* the tag */                                           \
+    "v_lshlrev_b32_e32 %[adr], 1, %[adrt]\n\t"                                                      \
+    "v_lshl_or_b32 %[hv], %[t3], 16, %[adrt]\n\t"                                                   \
+    "ds_read_u16 %[ent], %[adr]\n\t" /* the new window's entries */                                 \
+    "ds_read_u8 %[entt], %[adrt] offset:%[tagb]\n\t"                                                \
+    "v_alignbit_b32 %[t0], %[hv], %[hv], 16\n\t"                                                    \
+    "v_add_u32_e32 %[t0], 0x10000, %[t0]\n\t" /* w = (slot + 1) << 16 | tag */                      \
+    "v_cmp_ge_i32_e32 vcc, %[s1], %[lane]\n\t" /* probe lanes: <= 62, not past L - 16 */            \
+    "v_and_or_b32 %[word], %[hv], %[s2], %[t2]\n\t"                                                 \
+    "s_mov_b64 %[mwin], vcc\n\t"                                                                    \
+    "v_add_u32_dpp %[t1], %[t0], %[pdl1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
+    "v_bitop3_b32 %[pdnz], %[t0], %[t1], %[s0] bitop3:0x6c\n\t"                                     \
+    "v_or_b32_e32 %[t3], 0x1000000, %[word]\n\t"                                                    \
+    K1R_WIN_STEP("%[t4]")                                                                           \
+    "v_cndmask_b32_e32 %[word], %[t3], %[word], vcc\n\t" /* bit 24: never a hit */                  \
+    K1R_WIN_STEP("%[pdc]")                                                                          \
+    "v_min3_u32 %[pdnz], %[pdnz], %[t4], %[pdc]\n\t"                                                \
+    K1R_WIN_PAIR K1R_WIN_PAIR K1R_WIN_PAIR K1R_WIN_PAIR K1R_WIN_PAIR /* distances 4 .. 13 */        \
+    "v_lshrrev_b32_e32 %[t3], 8, %[pdnz]\n\t" /* the distance */                                    \
+    "v_cmp_gt_u32_e32 vcc, 0x10000, %[pdnz]\n\t" /* there is a predecessor */                       \
+    "v_cmp_eq_u32_e64 %[hm], 1, %[t3]\n\t"                                                          \
+    "v_and_b32_e32 %[pdnz], 0xff, %[pdnz]\n\t"                                                      \
+    "v_add_u32_e32 %[t1], 1, %[lane]\n\t"                                                           \
+    "v_mov_b32_e32 %[t4], 0xffffff00\n\t"                                                           \
+    "v_subb_co_u32_e64 %[t1], %[hm], %[t1], %[t3], %[hm]\n\t" /* lane - pd + 1 - (pd == 1) */       \
+    "v_cndmask_b32_e32 %[t3], 0, %[t3], vcc\n\t"                                                    \
+    "v_cndmask_b32_e32 %[pdl1], %[t4], %[t1], vcc\n\t"                                              \
+    "v_sub_u32_e32 %[pdc], %[t2], %[t3]\n\t"                                                        \
+    "s_cmp_gt_u32 %[skip], %[skipmax]\n\t" /* as at the statement's entry */                        \
+    "s_cbranch_scc1 L%=_x3\n\t"                                                                     \
+    "s_branch L%=_top\n"
+static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is written out for DMAX 13");
+// the window state: read only (K1R_WINOPS_IN) or moved by the _win path
+#define K1R_WINOPS_NONE_OUT
+#define K1R_WINOPS_NONE_IN(SEGHI)                                                                   \
+    [q0] "s"(q0), [L] "s"(L), [lm16] "s"(L - 16), [mwin] "s"(m_win), [seghi] SEGHI,                 \
+    [lim0] "s"(__builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0)), \
+    [dv] "v"(dv), [pdl1] "v"(pdl1), [pdc] "v"(pdc), [pdnz] "v"(pdnz), [adr] "v"(adr), [adrt] "v"(adr >> 1), \
+    [word] "v"(word),
+#define K1R_WINOPS_PATH_OUT                                                                         \
+    , [q0] "+s"(q0), [mwin] "+s"(m_win), [lim0] "+s"(lim0), [dv] "+v"(dv), [hv] "+v"(hv), [pdl1] "+v"(pdl1), \
+      [pdc] "+v"(pdc), [pdnz] "+v"(pdnz), [adr] "+v"(adr), [adrt] "+v"(adrt), [word] "+v"(word)
+#define K1R_WINOPS_PATH_IN(SEGHI)                                                                   \
+    [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),
+#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN) \
     do {                                                                                            \
         uint32_t _m0s, _pf, _s0, _s1, _s2, _s3, _t0, _t1, _t2, _t3, _t4;                            \
         uint64_t _valid, _hm;                                                                       \
@@ -1073,6 +1194,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             DUAL_LOOP                                                                               \
             "L%=_x3:\n\ts_mov_b32 %[code], 3\n\ts_branch L%=_end\n"                                 \
             "L%=_x1:\n\ts_mov_b32 %[code], 1\n\ts_branch L%=_end\n"                                 \
+            WIN                                                                                     \
             "L%=_x2:\n\ts_mov_b32 %[code], 2\n\ts_branch L%=_end\n"                                 \
             "L%=_x4:\n\t" K1R_X4                                                                   \
             "L%=_far:\n\t" /* K1r64: the candidate's 256 bytes from the input */                    \
@@ -1102,12 +1224,9 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
               [m0s] "=&s"(_m0s), [pf] "=&s"(_pf), [s0] "=&s"(_s0), [s1] "=&s"(_s1), [s2] "=&s"(_s2),   \
               [s3] "=&s"(_s3), [valid] "=&s"(_valid), [hm] "=&s"(_hm), [ent] "+v"(e32),                \
               [entt] "+v"(et32), [tka] "+v"(tka), [tkb] "+v"(tkb), [t0] "=&v"(_t0), [t1] "=&v"(_t1),  \
-              [t2] "=&v"(_t2), [t3] "=&v"(_t3), [t4] "=&v"(_t4)                                        \
-            : [q0] "s"(q0), [L] "s"(L), [lm16] "s"(L - 16), [mwin] "s"(m_win), [seghi] SEGHI,         \
-              [lim0] "s"(__builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0)), \
-              [dv] "v"(dv),                                                                         \
-              [pdl1] "v"(pdl1), [pdc] "v"(pdc), [pdnz] "v"(pdnz), [adr] "v"(adr), [adrt] "v"(adr >> 1), \
-              [word] "v"(word), [lane] "v"(lane), [lane4] "v"(lane << 2), [srcb] "s"(src),            \
+              [t2] "=&v"(_t2), [t3] "=&v"(_t3), [t4] "=&v"(_t4) WIN_OUT                                \
+            : WIN_IN(SEGHI)                                                                         \
+              [lane] "v"(lane), [lane4] "v"(lane << 2), [srcb] "s"(src),                              \
               [sx] "s"(__builtin_amdgcn_read_exec()), /* exec here (the compiler reads it once) */     \
               [skipmax] "i"(64 - DMAX), [dmask] "i"((1u << DMAX) - 1), [lsmax] "i"(64 - SNAPPY_K1R_LSMIN), \
               [l0max] "i"(62 - SNAPPY_K1R_RMIN), [tagb] "i"(kTagBase), "{v[2:33]}"(g0), "{v[34:65]}"(g1), \
@@ -1153,6 +1272,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
                     rs_flush += r1 - r0;
                     rs_win += r2 - r1;
                 }
+                rs_gopen = rs_c2 && !rfl;
+                if (rs_gopen) {
+                    rs_gout += r0 - rs_ra1;
+                    rs_r2 = r2;
+                    rs_ng++;
+                }
+                rs_c2 = false;
                 rs_n++;
                 rs_nfl += rfl;
                 if (false)
@@ -1197,17 +1323,31 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #ifdef SNAPPY_K1R_RSTAMPS
                     uint64_t ra0, ra1;
                     RSTAMP(ra0);
+                    if (rs_gopen) rs_gin += ra0 - rs_r2;
+                    rs_gopen = false;
 #endif
-                    if constexpr (BIG)
+                    if constexpr (BIG) {
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND64, K1R_SEGHI64(seg_hi), K1R_HIT64, SNAPPY_K1R_PAD64,
-                                            K1R64_HALF_SEL, K1R64_HALF_LOOP);
-                    else
-                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "");
+                                            K1R64_HALF_SEL, K1R64_HALF_LOOP, K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN);
+                    } else {
+#if SNAPPY_K1R_WIN_INLOOP
+                        // (m_win17 is read by the C++ round alone: made there from q0 and L)
+                        int32_t lim0 = __builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0);
+                        uint32_t adrt = adr >> 1;
+                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
+                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN);
+#else
+                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
+                                            K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN);
+#endif
+                    }
 #ifdef SNAPPY_K1R_RSTAMPS
                     RSTAMP(ra1);
                     rs_asm += ra1 - ra0;
                     rs_nasm++;
                     rs_code[code < 6 ? code : 0]++;
+                    rs_ra1 = ra1;
+                    rs_c2 = code == 2;
 #endif
                     ent = (uint16_t)e32;
                     ent_t = (uint8_t)et32;
@@ -1259,7 +1399,12 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
                 if (__builtin_expect(skip > 64 - DMAX, 0)) {
                     const uint32_t kcap = 64 - skip;
                     valid = ((2ull << kcap) - 1) << lane0;
-                    if (lane0 + kcap < 64) valid &= ~((1ull << (lane0 + kcap)) & ~m_win17);
+                    uint64_t mw17 = m_win17;
+#if K1R_ASM_ROUNDS && SNAPPY_K1R_WIN_INLOOP
+                    if constexpr (!BIG)  // the window may have moved inside the asm statement
+                        mw17 = __ballot((int32_t)lane <= (int32_t)(L - 17 - q0) && lane <= 62);
+#endif
+                    if (lane0 + kcap < 64) valid &= ~((1ull << (lane0 + kcap)) & ~mw17);
                     valid &= m_win;
                 }
                 // lane l > lane0 takes the in-round candidate when its nearest same-hash lane is >= lane0 - 1;
@@ -1455,9 +1600,10 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #ifdef SNAPPY_K1R_RSTAMPS
     if (lane == 0) {
         uint64_t *st = reinterpret_cast<uint64_t *>(tokens + (uint64_t)gridDim.x * tok_cap) + 4 * (uint64_t)u;
-        st[0] = clock64() - t_loop;
-        st[1] = rs_flush | (rs_asm << 24);  // (a unit's flush cycles < 2^24)
-        st[2] = rs_win | ((uint64_t)rs_nasm << 40);
+        // (a unit's loop cycles < 2^30, its flush and window cycles < 2^24, glue cycles < 2^22)
+        st[0] = (clock64() - t_loop) | (rs_gout << 30) | ((uint64_t)rs_ng << 52);
+        st[1] = rs_flush | (rs_asm << 24);
+        st[2] = rs_win | (rs_gin << 24) | ((uint64_t)rs_nasm << 46);
         st[3] = rs_n | ((uint64_t)rs_nfl << 16) | ((uint64_t)rs_code[3] << 32) | ((uint64_t)(rs_code[4] + rs_code[5]) << 48);
     }
 #endif
