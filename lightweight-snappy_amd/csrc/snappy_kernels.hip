@@ -786,8 +786,15 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     const uint64_t t_loop = clock64();
     uint64_t rs_flush = 0, rs_win = 0, rs_asm = 0;
     uint32_t rs_n = 0, rs_nfl = 0, rs_nasm = 0, rs_code[6] = {0, 0, 0, 0, 0, 0};
-    // the glue around a code-2 refresh without a token flush: from the asm statement's
-    // end to the start of the window move, and from the refresh's end to the statement
+    // the glue around one group of exits from the asm statement: from the statement's
+    // end to the first useful instruction outside, and from the last one to the
+    // statement.  SNAPPY_K1R_RSTAMPS_GROUP: 1 = code-2 refreshes without a token flush
+    // (to the start of the window move, from the refresh's end), 2 = code-2 refreshes
+    // with one (to the start of the flush), 4 / 5 = the code-4 / code-5 exits that come
+    // back (to the start of the C++ branch that finishes the round, from its end)
+#ifndef SNAPPY_K1R_RSTAMPS_GROUP
+#define SNAPPY_K1R_RSTAMPS_GROUP 1
+#endif
     uint64_t rs_gout = 0, rs_gin = 0, rs_ra1 = 0, rs_r2 = 0;
     uint32_t rs_ng = 0;
     bool rs_c2 = false, rs_gopen = false;
@@ -806,10 +813,12 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     // first differing byte; a round without a hit inserts its nk probes.  It
     // leaves the loop with `code`: 1 = skip past the step-1 range or
     // is_block_end, 2 = the window must move (K1r64; K1r moves it inside the
-    // statement, K1R_WIN_PATH, and leaves only when a token flush is due), 3 = the next round's
+    // statement, K1R_WIN_PATH, with the token flush when one is due, K1R_FLUSH_PATH, and leaves
+    // only for a flush that holds a long-form token), 3 = the next round's
     // probes reach a step of 2 (skip > 64 - DMAX: the C++ round), and mid-round
     // (inserts done, entries read) 4 = 64 or more equal bytes (C++ extends the
-    // match), 5 = a tag collision (C++ finishes the miss).  Everything the
+    // match), 5 = a tag collision (K1r64: C++ finishes the miss; K1r finishes it inside the
+    // statement, K1R_X5_PATH).  Everything the
     // compiler schedules around it -- waits, DPP, cross-lane reads -- is
     // written out with its wait states: a VALU-written SGPR or VCC is read by
     // VALU two states later (v_cndmask, v_readlane sources); LDS results are
@@ -874,7 +883,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // With the window refresh inside K1r's statement (profiles/r08b_*): PAD32 0..15 ->
 // 11.12-11.14 (2 and 10) to 11.46-11.49 (15) ms per GiB, the parent 11.91-11.92.
 #ifndef SNAPPY_K1R_PAD32
-#define SNAPPY_K1R_PAD32 2  // with SNAPPY_K1R_WIN_INLOOP (profiles/r08b_*)
+#define SNAPPY_K1R_PAD32 2  // with SNAPPY_K1R_WIN_INLOOP (profiles/r08b_*), and again with the flush and the
+                            // tag-collision round inside the statement (r09b_*: 2 and 10 best of 0..15)
 #endif
 #ifndef SNAPPY_K1R_PAD64
 #define SNAPPY_K1R_PAD64 0  // with SNAPPY_K1R64_HALF32 (profiles/r06aa_*, r06ad_*)
@@ -1095,8 +1105,164 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 #ifndef SNAPPY_K1R_WIN_INLOOP
 #define SNAPPY_K1R_WIN_INLOOP 1
 #endif
+// SNAPPY_K1R_FLUSH_INLOOP: the token flush of a refresh (pend + dkn > 48: 74 of a
+// 32 KiB text unit's refreshes) as a path of K1r's statement instead of a code-2
+// exit, the C++ flush_tokens() and WINDOW_LS and a re-entry.  _fl does what
+// flush_tokens() does for tokens of the short form and goes on into the refresh
+// (_wr); the deferred token stays pending.  Per lane: pos / len / end from tka,
+// prev = the end of the lane before (wave_shr:1 without bound_ctrl: lane 0 keeps
+// cend), litn = pos - prev.  A token whose len - 4 or litn does not fit 8 bits
+// needs the second store (tok_full): one ballot over the lanes below pend sends
+// those flushes to _x2 before anything but temporaries is written, and the C++
+// flush runs as it always did (so len <= 258 and litn <= 254 below; the sizes are
+// literal_bytes() and copy_bytes() for every length all the same).  64 pending
+// tokens leave too: s_bfm_b64 takes its count modulo 64.  The token words go out
+// in one global_store_dword (scalar base, lane offset 4 (nt + lane)) under the
+// mask of the lanes below pend; the encoded sizes are summed by the DPP scan of
+// wave_incl_scan (every DPP read two states behind the write of its source);
+// at most one lane, t = (0 - nt) & 255, starts a K2 segment: found in scalar
+// code, its record (acc + ex, prev) stored by two global_store_dword under a
+// one-lane mask.  exec is sx again after each store group.  Temporaries: t0-t4
+// until the ballot, then the window's lane data, which the refresh writes anew
+// (pdl1, pdc, pdnz, word, hv); the old window's entry reads may still be in
+// flight, so ent / entt are not touched.  m0 is not read.  nt, acc and cend are
+// in/out operands, the unit's token and segment-record bases scalar inputs.
+// A/B on 1 GiB of 32 KiB text streams, outputs identical (profiles/r09b_*): the
+// parent 11.12-11.13 ms, with this path 10.98-10.99, with K1R_X5_PATH as well
+// 10.91-10.94; a unit enters the statement 10.5 times instead of 111 (r09a_*).
+// SNAPPY_K1R_FLUSH_INLOOP 0 is the parent's flow and operand list.
+#ifndef SNAPPY_K1R_FLUSH_INLOOP
+#define SNAPPY_K1R_FLUSH_INLOOP 1
+#endif
+#if SNAPPY_K1R_FLUSH_INLOOP
+#define K1R_FLUSH_TARGET "_fl"
+#define K1R_FLUSH_SCAN(ctrl) "v_add_u32_dpp %[pdc], %[pdc], %[pdc] " ctrl " bank_mask:0xf bound_ctrl:1\n\t"
+#define K1R_FLUSH_PATH                                                                              \
+    "L%=_fl:\n\t"                                                                                   \
+    "s_cmp_gt_u32 %[pend], 63\n\t"                                                                  \
+    "s_cbranch_scc1 L%=_x2\n\t"                                                                     \
+    "v_and_b32_e32 %[t0], 0xffff, %[tka]\n\t" /* pos */                                             \
+    "v_lshrrev_b32_e32 %[t1], 16, %[tka]\n\t" /* len */                                             \
+    "v_mov_b32_e32 %[t3], %[cend]\n\t"                                                              \
+    "v_add_u32_e32 %[t2], %[t0], %[t1]\n\t" /* end */                                               \
+    "s_bfm_b64 %[valid], %[pend], 0\n\t" /* the lanes below pend */                                 \
+    "v_add_u32_e32 %[t4], -4, %[t1]\n\t"                                                            \
+    "s_movk_i32 %[s0], 0xfe\n\t"                                                                    \
+    "v_mov_b32_dpp %[t3], %[t2] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" /* prev */               \
+    "v_cmp_lt_u32_e32 vcc, %[s0], %[t4]\n\t" /* len - 4 >= 255 */                                   \
+    "v_sub_u32_e32 %[t0], %[t0], %[t3]\n\t" /* litn */                                              \
+    "v_cmp_lt_u32_e64 %[hm], %[s0], %[t0]\n\t" /* litn >= 255 */                                    \
+    "s_or_b64 %[hm], %[hm], vcc\n\t"                                                                \
+    "s_and_b64 %[hm], %[hm], %[valid]\n\t"                                                          \
+    "s_cbranch_scc1 L%=_x2\n\t" /* a long-form token: the C++ flush, from untouched state */        \
+    "v_lshlrev_b32_e32 %[t4], 16, %[t4]\n\t"                                                        \
+    "v_lshl_add_u32 %[pdl1], %[nt], 2, %[lane4]\n\t" /* 4 (nt + lane) */                            \
+    "v_lshl_or_b32 %[t4], %[t0], 24, %[t4]\n\t"                                                     \
+    "v_or_b32_e32 %[t4], %[t4], %[tkb]\n\t" /* off | (len - 4) << 16 | litn << 24 */                \
+    "s_mov_b64 exec, %[valid]\n\t"                                                                  \
+    "global_store_dword %[pdl1], %[t4], %[tokb]\n\t"                                                \
+    "s_mov_b64 exec, %[sx]\n\t"                                                                     \
+    "v_cmp_lt_u32_e32 vcc, 60, %[t0]\n\t" /* literal_bytes(litn) */                                 \
+    "v_add_u32_e32 %[pdnz], -5, %[t1]\n\t" /* copy_bytes(len, off): n64 = max(len - 5, 0) >> 6 */   \
+    "v_max_i32_e32 %[pdnz], 0, %[pdnz]\n\t"                                                         \
+    "v_addc_co_u32_e32 %[pdc], vcc, 1, %[t0], vcc\n\t" /* litn + 1 + (litn > 60) */                 \
+    "v_cmp_lt_u32_e32 vcc, 0x100, %[t0]\n\t"                                                        \
+    "v_lshrrev_b32_e32 %[pdnz], 6, %[pdnz]\n\t"                                                     \
+    "v_lshlrev_b32_e32 %[word], 6, %[pdnz]\n\t"                                                     \
+    "v_addc_co_u32_e32 %[pdc], vcc, 0, %[pdc], vcc\n\t" /* + (litn > 256) */                        \
+    "v_cmp_ne_u32_e32 vcc, 0, %[t0]\n\t"                                                            \
+    "v_sub_u32_e32 %[word], %[t1], %[word]\n\t" /* rem = len - 64 n64: 4 .. 68 */                   \
+    "v_add_u32_e32 %[hv], -12, %[word]\n\t"                                                         \
+    "v_cndmask_b32_e32 %[pdc], 0, %[pdc], vcc\n\t" /* no literal: no bytes */                       \
+    "v_cmp_lt_u32_e32 vcc, 64, %[word]\n\t" /* has60 */                                             \
+    "s_movk_i32 %[s1], 52\n\t"                                                                      \
+    "s_sub_u32 %[s0], 0, %[nt]\n\t"                                                                 \
+    "v_addc_co_u32_e32 %[pdnz], vcc, 0, %[pdnz], vcc\n\t" /* n64 + has60 */                         \
+    "v_cmp_lt_u32_e64 %[hm], %[s1], %[hv]\n\t" /* last < 12: rem < 12 or rem > 64 */                \
+    "v_cmp_gt_u32_e32 vcc, 0x800, %[tkb]\n\t" /* off < 2048 */                                      \
+    "v_mad_u32_u24 %[pdnz], %[pdnz], 3, 3\n\t"                                                      \
+    "s_and_b64 vcc, vcc, %[hm]\n\t"                                                                 \
+    "s_and_b32 %[s0], %[s0], 0xff\n\t" /* t: the lane whose token starts a K2 segment */            \
+    "v_subb_co_u32_e64 %[pdnz], %[hm], %[pdnz], 0, vcc\n\t" /* 2 bytes, not 3, for a short near copy */ \
+    "s_add_u32 %[s1], %[nt], %[s0]\n\t"                                                             \
+    "s_add_u32 %[s2], %[pend], -1\n\t"                                                              \
+    "v_add_u32_e32 %[pdc], %[pdc], %[pdnz]\n\t"                                                     \
+    "v_cndmask_b32_e64 %[pdc], 0, %[pdc], %[valid]\n\t" /* b: the lanes from pend on count 0 */     \
+    "v_mov_b32_e32 %[pdnz], %[pdc]\n\t"                                                             \
+    "s_lshr_b32 %[s1], %[s1], 8\n\t"                                                                \
+    K1R_FLUSH_SCAN("row_shr:1 row_mask:0xf")                                                        \
+    "s_lshl_b32 %[s1], %[s1], 3\n\t" /* the byte offset of segment (nt + t) / 256's record */       \
+    "v_readlane_b32 %[cend], %[t2], %[s2]\n\t" /* the end of the last token */                         \
+    K1R_FLUSH_SCAN("row_shr:2 row_mask:0xf")                                                        \
+    "s_nop 1\n\t"                                                                                   \
+    K1R_FLUSH_SCAN("row_shr:4 row_mask:0xf")                                                        \
+    "s_nop 1\n\t"                                                                                   \
+    K1R_FLUSH_SCAN("row_shr:8 row_mask:0xf")                                                        \
+    "s_nop 1\n\t"                                                                                   \
+    K1R_FLUSH_SCAN("row_bcast:15 row_mask:0xa")                                                     \
+    "s_nop 1\n\t"                                                                                   \
+    K1R_FLUSH_SCAN("row_bcast:31 row_mask:0xc")                                                     \
+    "s_cmp_lt_u32 %[s0], %[pend]\n\t"                                                               \
+    "v_readlane_b32 %[s3], %[pdc], 63\n\t" /* the flush's bytes */                                  \
+    "v_sub_u32_e32 %[pdc], %[pdc], %[pdnz]\n\t"                                                     \
+    "v_add_u32_e32 %[pdc], %[acc], %[pdc]\n\t" /* acc + ex */                                       \
+    "s_cbranch_scc0 L%=_fl2\n\t"                                                                    \
+    "s_bfm_b64 exec, 1, %[s0]\n\t" /* lane t alone */                                               \
+    "v_mov_b32_e32 %[word], %[s1]\n\t"                                                              \
+    "global_store_dword %[word], %[pdc], %[segb]\n\t"                                               \
+    "global_store_dword %[word], %[t3], %[segb] offset:4\n\t"                                       \
+    "s_mov_b64 exec, %[sx]\n"                                                                       \
+    "L%=_fl2:\n\t"                                                                                  \
+    "s_add_u32 %[acc], %[acc], %[s3]\n\t"                                                           \
+    "s_add_u32 %[nt], %[nt], %[pend]\n\t"                                                           \
+    "s_mov_b32 %[pend], 0\n\t"                                                                      \
+    "s_branch L%=_wr\n"
+#define K1R_FLUSHOPS_OUT , [nt] "+s"(nt), [acc] "+s"(acc), [cend] "+s"(cend)
+#define K1R_FLUSHOPS_IN [tokb] "s"(tok), [segb] "s"(segu),
+#else
+#define K1R_FLUSH_TARGET "_x2"
+#define K1R_FLUSH_PATH
+#define K1R_FLUSHOPS_OUT
+#define K1R_FLUSHOPS_IN
+#endif
+// SNAPPY_K1R_X5_INLOOP: a tag collision (the verification found fewer than 4
+// equal bytes: 27 rounds of a 32 KiB text unit) finishes as a miss inside K1r's
+// statement instead of leaving with code 5.  _x5 is the C++ code-5 branch in
+// scalar code: the skip fix first (the pending flag is still the previous
+// round's: this round's K1R_DK_LATE has not run), no deferred token, the inserts
+// of lanes lane0 - 1 .. lane0 and fresh entry reads when the collision was on the
+// round's first probe lane (the round inserted lane f alone then), p, skip and
+// lane0 as after a miss at f, and the miss round's way on.  K1r64's statement
+// keeps the exit (K1R_X5_EXIT).  SNAPPY_K1R_X5_INLOOP 0 is the parent's flow.
+#ifndef SNAPPY_K1R_X5_INLOOP
+#define SNAPPY_K1R_X5_INLOOP 1
+#endif
+#define K1R_X5_EXIT "L%=_x5:\n\ts_mov_b32 %[code], 5\n"
+#define K1R_X5_PATH                                                                                 \
+    "L%=_x5:\n\t"                                                                                   \
+    K1R_SKIPFIX                                                                                     \
+    "s_mov_b32 %[dkn], 0\n\t"                                                                       \
+    "s_cmp_lg_u32 %[f], %[lane0]\n\t"                                                               \
+    "s_cbranch_scc1 L%=_x5b\n\t"                                                                    \
+    "s_add_i32 %[s1], %[lane0], -1\n\t"                                                             \
+    K1R_INSERTS("2", "%[s1]") /* its p - 1, then p again (the higher lane wins a shared slot) */    \
+    "L%=_x5b:\n\t"                                                                                  \
+    "s_sub_u32 %[s0], %[f], %[lane0]\n\t"                                                           \
+    "s_add_u32 %[s1], %[skip], %[s0]\n\t"                                                           \
+    "s_lshr_b32 %[s1], %[s1], 5\n\t"                                                                \
+    "s_add_u32 %[p], %[pf], %[s1]\n\t" /* pf + ((skip + f - lane0) >> 5) */                         \
+    "s_add_u32 %[skip], %[skip], %[s0]\n\t"                                                         \
+    "s_add_u32 %[skip], %[skip], 1\n\t"                                                             \
+    "s_sub_u32 %[lane0], %[p], %[q0]\n\t"                                                           \
+    K1R_NOHIT_TAIL("")                                                                              \
+    "s_branch L%=_x3\n"
+#if SNAPPY_K1R_X5_INLOOP
+#define K1R_X5_32 K1R_X5_PATH
+#else
+#define K1R_X5_32 K1R_X5_EXIT
+#endif
 #define K1R_WIN_NONE "L%=_win:\n"
-#define K1R_WIN_STEP(dst)                                                                           \
+#define K1R_WIN_STEP(dst)                                                                          \
     "v_add_u32_dpp %[t1], %[t1], %[pdl1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
     "v_bitop3_b32 " dst ", %[t0], %[t1], %[s0] bitop3:0x6c\n\t" /* shifted ^ (w & 0xFFFF0000) */
 #define K1R_WIN_PAIR                                                                                \
@@ -1108,8 +1274,9 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "L%=_win:\n\t"                                                                                  \
     K1R_SKIPFIX                                                                                     \
     "s_add_u32 %[s0], %[pend], %[dkn]\n\t"                                                          \
-    "s_cmp_gt_u32 %[s0], 48\n\t" /* a token flush is due: the C++ refresh */                        \
-    "s_cbranch_scc1 L%=_x2\n\t"                                                                     \
+    "s_cmp_gt_u32 %[s0], 48\n\t" /* a token flush is due: K1R_FLUSH_PATH, or the C++ refresh */     \
+    "s_cbranch_scc1 L%=" K1R_FLUSH_TARGET "\n"                                                      \
+    "L%=_wr:\n\t"                                                                                   \
     "s_add_u32 %[q0], %[p], -1\n\t"                                                                 \
     "s_lshr_b32 %[s0], %[q0], 8\n\t"                                                                \
     "s_bfe_u32 %[s1], %[q0], 0x60002\n\t" /* dr */                                                  \
@@ -1166,8 +1333,12 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "v_sub_u32_e32 %[pdc], %[t2], %[t3]\n\t"                                                        \
     "s_cmp_gt_u32 %[skip], %[skipmax]\n\t" /* as at the statement's entry */                        \
     "s_cbranch_scc1 L%=_x3\n\t"                                                                     \
-    "s_branch L%=_top\n"
+    "s_branch L%=_top\n"                                                                            \
+    K1R_FLUSH_PATH
 static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is written out for DMAX 13");
+static_assert(SNAPPY_K1R_WIN_INLOOP || !SNAPPY_K1R_FLUSH_INLOOP, "K1R_FLUSH_PATH falls into K1R_WIN_PATH's refresh");
+static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
+              "K1R_FLUSH_PATH: one segment record per flush at most, its lane (0 - nt) & 255");
 // the window state: read only (K1R_WINOPS_IN) or moved by the _win path
 #define K1R_WINOPS_NONE_OUT
 #define K1R_WINOPS_NONE_IN(SEGHI)                                                                   \
@@ -1177,10 +1348,11 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
     [word] "v"(word),
 #define K1R_WINOPS_PATH_OUT                                                                         \
     , [q0] "+s"(q0), [mwin] "+s"(m_win), [lim0] "+s"(lim0), [dv] "+v"(dv), [hv] "+v"(hv), [pdl1] "+v"(pdl1), \
-      [pdc] "+v"(pdc), [pdnz] "+v"(pdnz), [adr] "+v"(adr), [adrt] "+v"(adrt), [word] "+v"(word)
+      [pdc] "+v"(pdc), [pdnz] "+v"(pdnz), [adr] "+v"(adr), [adrt] "+v"(adrt), [word] "+v"(word) K1R_FLUSHOPS_OUT
 #define K1R_WINOPS_PATH_IN(SEGHI)                                                                   \
-    [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),
-#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN) \
+    [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),    \
+    K1R_FLUSHOPS_IN
+#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5) \
     do {                                                                                            \
         uint32_t _m0s, _pf, _s0, _s1, _s2, _s3, _t0, _t1, _t2, _t3, _t4;                            \
         uint64_t _valid, _hm;                                                                       \
@@ -1213,7 +1385,7 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
             "v_cndmask_b32_e32 %[t3], v2, v129, vcc\n\t"                                            \
             "ds_bpermute_b32 %[t3], %[t1], %[t3]\n\t"                                               \
             "s_branch L%=_farret\n"                                                                 \
-            "L%=_x5:\n\ts_mov_b32 %[code], 5\n"                                                     \
+            X5                                                                                      \
             "L%=_end:\n\t"                                                                          \
             K1R_SKIPFIX                                                                             \
             "s_mov_b32 m0, %[m0s]\n\t"                                                              \
@@ -1272,7 +1444,7 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
                     rs_flush += r1 - r0;
                     rs_win += r2 - r1;
                 }
-                rs_gopen = rs_c2 && !rfl;
+                rs_gopen = rs_c2 && (SNAPPY_K1R_RSTAMPS_GROUP == 1 ? !rfl : SNAPPY_K1R_RSTAMPS_GROUP == 2 && rfl);
                 if (rs_gopen) {
                     rs_gout += r0 - rs_ra1;
                     rs_r2 = r2;
@@ -1328,17 +1500,18 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
 #endif
                     if constexpr (BIG) {
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND64, K1R_SEGHI64(seg_hi), K1R_HIT64, SNAPPY_K1R_PAD64,
-                                            K1R64_HALF_SEL, K1R64_HALF_LOOP, K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN);
+                                            K1R64_HALF_SEL, K1R64_HALF_LOOP, K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN,
+                                            K1R_X5_EXIT);
                     } else {
 #if SNAPPY_K1R_WIN_INLOOP
                         // (m_win17 is read by the C++ round alone: made there from q0 and L)
                         int32_t lim0 = __builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0);
                         uint32_t adrt = adr >> 1;
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
-                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN);
+                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN, K1R_X5_32);
 #else
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
-                                            K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN);
+                                            K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN, K1R_X5_32);
 #endif
                     }
 #ifdef SNAPPY_K1R_RSTAMPS
@@ -1358,6 +1531,10 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
                         continue;
                     }
                     if (code >= 4) {  // the round stopped after its inserts: finish it here
+#ifdef SNAPPY_K1R_RSTAMPS
+                        uint64_t g0, g1;
+                        RSTAMP(g0);
+#endif
                         const uint32_t f = fx, pf = q0 + fx, c = cx;
                         uint32_t np;
                         if (code == 4) {  // 64 or more equal bytes: extend the match
@@ -1384,6 +1561,15 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
                             refresh();
                             lane0 = 1;
                         }
+#ifdef SNAPPY_K1R_RSTAMPS
+                        RSTAMP(g1);
+                        if (code == SNAPPY_K1R_RSTAMPS_GROUP) {
+                            rs_gout += g0 - rs_ra1;
+                            rs_r2 = g1;
+                            rs_gopen = true;
+                            rs_ng++;
+                        }
+#endif
                         continue;
                     }
                     // code 3: a round whose probes reach a step of 2 (skip > 64 - DMAX) runs below
@@ -1604,7 +1790,9 @@ static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is 
         st[0] = (clock64() - t_loop) | (rs_gout << 30) | ((uint64_t)rs_ng << 52);
         st[1] = rs_flush | (rs_asm << 24);
         st[2] = rs_win | (rs_gin << 24) | ((uint64_t)rs_nasm << 46);
-        st[3] = rs_n | ((uint64_t)rs_nfl << 16) | ((uint64_t)rs_code[3] << 32) | ((uint64_t)(rs_code[4] + rs_code[5]) << 48);
+        // (refreshes, flushes and code-3 exits of a unit < 2^12, code-4 and code-5 exits < 2^14)
+        st[3] = rs_n | ((uint64_t)rs_nfl << 12) | ((uint64_t)rs_code[3] << 24) | ((uint64_t)rs_code[4] << 36) |
+                ((uint64_t)rs_code[5] << 50);
     }
 #endif
 #ifdef SNAPPY_K1R_STATS

@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """Window-refresh share of K1r / K1r64 with the asm round loop in place
 (SNAPPY_K1R_RSTAMPS build): loop cycles per unit, token-flush and window-move
-cycles per refresh, and the glue around a refresh that leaves the asm statement
-without a token flush (from the statement's end to the window move, from the
-refresh's end back to the statement; -DSNAPPY_K1R_WIN_INLOOP=0 builds the flow
-in which every refresh leaves).  Usage: tools/k1r_rstamps.py BYTES CHUNK [VARIANT]
-(VARIANT: tools/build_pads.sh 'rst:-DSNAPPY_K1R_RSTAMPS')"""
+cycles per refresh, exits from the asm statement by code, and the glue around
+one group of exits (from the statement's end to the first useful instruction
+outside, from the last one back to the statement).  The build picks the group
+with -DSNAPPY_K1R_RSTAMPS_GROUP=: 1 code-2 refreshes without a token flush,
+2 code-2 refreshes with one, 4 / 5 the code-4 / code-5 exits that come back.
+-DSNAPPY_K1R_WIN_INLOOP=0, -DSNAPPY_K1R_FLUSH_INLOOP=0 and
+-DSNAPPY_K1R_X5_INLOOP=0 build the flows in which those exits still happen.
+Usage: tools/k1r_rstamps.py BYTES CHUNK [VARIANT [GROUP]]
+(VARIANT: tools/build_pads.sh 'rst:-DSNAPPY_K1R_RSTAMPS'; GROUP: the group the
+variant was built with, for the label)"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lightweight-snappy_amd"))
@@ -15,6 +20,7 @@ import numpy as np, torch
 import datagen, snappy_amd
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256 << 20
 chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 32768
+group = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 layout = snappy_amd.SINGLE if chunk == 65536 else snappy_amd.STREAMS
 a = datagen.make("T", n, 1234)
 x = torch.from_numpy(a).cuda()
@@ -38,13 +44,16 @@ loop = f(raw[:, 0] & ((1 << 30) - 1))
 gout, ng = f((raw[:, 0] >> 30) & ((1 << 22) - 1)), f(raw[:, 0] >> 52)
 fl, asm = f(raw[:, 1] & ((1 << 24) - 1)), f(raw[:, 1] >> 24)
 win, gin, nasm = f(raw[:, 2] & ((1 << 24) - 1)), f((raw[:, 2] >> 24) & ((1 << 22) - 1)), f(raw[:, 2] >> 46)
-nref, nfl = f(raw[:, 3] & 0xFFFF), f((raw[:, 3] >> 16) & 0xFFFF)
-c3, c45 = f((raw[:, 3] >> 32) & 0xFFFF), f(raw[:, 3] >> 48)
-print(f"chunk {chunk}: loop {loop:.0f} cycles/unit; refreshes {nref:.0f}/unit ({nfl:.0f} with a token flush)")
-print(f"  asm round loop {asm/loop*100:5.1f}%  {nasm:.0f} entries/unit, {asm/max(nasm,1):.0f} cycles/entry; exits to the C++ round: code 3 {c3:.0f}, codes 4-5 {c45:.0f}")
+nref, nfl = f(raw[:, 3] & 0xFFF), f((raw[:, 3] >> 12) & 0xFFF)
+c3, c4, c5 = f((raw[:, 3] >> 24) & 0xFFF), f((raw[:, 3] >> 36) & 0x3FFF), f(raw[:, 3] >> 50)
+what = {1: "code-2 refreshes without a flush", 2: "code-2 refreshes with a token flush",
+        4: "code-4 exits that come back", 5: "code-5 exits that come back"}[group]
+print(f"chunk {chunk}: loop {loop:.0f} cycles/unit; refreshes in C++ {nref:.1f}/unit ({nfl:.1f} with a token flush)")
+print(f"  asm round loop {asm/loop*100:5.1f}%  {nasm:.1f} entries/unit, {asm/max(nasm,1):.0f} cycles/entry; exits by code: "
+      f"1 and 2 {nasm-c3-c4-c5:.1f}, 3 {c3:.1f}, 4 {c4:.2f}, 5 {c5:.2f}")
 print(f"  window move    {win/loop*100:5.1f}%  {win/max(nref,1):6.0f} cycles/refresh (s_memtime clock)")
-print(f"  token flush    {fl/loop*100:5.1f}%  {fl/max(nfl,1):6.0f} cycles/flush")
-print(f"  code-2 refreshes without a flush: {ng:.0f}/unit; glue from the asm statement's end to the window move "
-      f"{gout/max(ng,1):.0f} cycles/refresh, from the refresh's end to the statement {gin/max(ng,1):.0f} "
-      f"(each holds one stamp; {(gout+gin)/loop*100:.1f}% of the loop)")
+print(f"  token flush    {fl/loop*100:5.1f}%  {fl/max(nfl,1e-9):6.0f} cycles/flush")
+print(f"  {what}: {ng:.2f}/unit; glue from the asm statement's end to the first useful instruction "
+      f"{gout/max(ng,1e-9):.0f} cycles/exit, from the last one to the statement {gin/max(ng,1e-9):.0f} "
+      f"(each holds one stamp; {(gout+gin)/loop*100:.2f}% of the loop)")
 print(f"  rest (C++ rounds, W-probe rounds, stamps) {(loop-asm-win-fl)/loop*100:5.1f}%")
