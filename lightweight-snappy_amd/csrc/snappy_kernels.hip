@@ -2731,7 +2731,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
 #if SNAPPY_K4_JSIZE == 2
                 const uint32_t k = __builtin_elementwise_sub_sat(m, 59u);
                 const uint32_t lv = k ? b4 & (0xFFFFFFFFu >> ((32 - 8 * k) & 31)) : m;
-                const uint32_t xsize = t == 0 ? lv + k + 2 : (0x5320u >> (4 * t)) & 0xF;
+                const uint32_t xsize = t == 0 ? __builtin_elementwise_add_sat(lv, k + 2) : (0x5320u >> (4 * t)) & 0xF;
                 const uint32_t size = t == 0 ? (m < 60 ? m + 2 : 64u) : (0x5320u >> (4 * t)) & 0xF;
 #elif SNAPPY_K4_JSIZE
                 // for the jumps only: a literal with m >= 60 is >= 63 bytes, taken as
@@ -2741,7 +2741,8 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
 #else
                 const uint32_t k = __builtin_elementwise_sub_sat(m, 59u);
                 const uint32_t lv = k ? b4 & (0xFFFFFFFFu >> ((32 - 8 * k) & 31)) : m;
-                const uint32_t size = t == 0 ? lv + k + 2 : (0x5320u >> (4 * t)) & 0xF;
+                // (saturating: a 4-byte length of 2^32 - 1 .. 2^32 - 6 must not wrap to a small size)
+                const uint32_t size = t == 0 ? __builtin_elementwise_add_sat(lv, k + 2) : (0x5320u >> (4 * t)) & 0xF;
 #endif
                 // positions as ds_bpermute addresses (4 x position); one >= 256 has
                 // left the 64 and must stay >= 256 (its exact value is never used).
@@ -2771,6 +2772,9 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
                 hx0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)pos4, (int)x0);
                 hb4 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)pos4, (int)b4);
                 const uint32_t last = (uint32_t)__builtin_amdgcn_readlane(pos4, hE - 1) >> 2;
+                // (with a saturated size, last + 0xFFFFFFFF wraps to last - 1: a further half may
+                // then be parsed from inside this one.  Harmless: its garbage elements take lanes
+                // after the oversized literal, which is refused as TRUNCATED, and nexec cuts there)
 #if SNAPPY_K4_JSIZE == 2
                 hexit = last + (uint32_t)__builtin_amdgcn_readlane(xsize, last);
 #elif SNAPPY_K4_JSIZE
@@ -2782,7 +2786,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
                     asm("s_max_u32 %0, %1, 59" : "=s"(lk) : "s"(lm) : "scc");
                     lk -= 59;
                     const uint32_t llv = lk ? lb & (0xFFFFFFFFu >> ((32 - 8 * lk) & 31)) : lm;
-                    hexit = last + (lt == 0 ? llv + lk + 2 : (0x5320u >> (4 * lt)) & 0xF);
+                    hexit = last + (lt == 0 ? __builtin_elementwise_add_sat(llv, lk + 2) : (0x5320u >> (4 * lt)) & 0xF);
                 }
 #else
                 hexit = last + (uint32_t)__builtin_amdgcn_readlane(size, last);
@@ -2841,9 +2845,13 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
             const uint32_t k = __builtin_elementwise_sub_sat(m, 59u);  // literal: extra length bytes
             const uint32_t lx = eb4 & (0xFFFFFFFFu >> ((32 - 8 * k) & 31));
             const uint32_t lv = k ? lx : m;
-            const uint32_t l_olen = lv + 1, c1_olen = (m & 7) + 4, c_olen = m + 1;
+            // a literal's length and size saturate at 2^32 - 1: a 4-byte length field of
+            // 2^32 - 1 (2^32 bytes) would wrap to e_len = 0, e_size = 5 and pass every check
+            // below; saturated it is past any unit (clen < 2^31) and refused as TRUNCATED
+            const uint32_t l_olen = __builtin_elementwise_add_sat(lv, 1u), c1_olen = (m & 7) + 4, c_olen = m + 1;
             const uint32_t c1b = ((tag >> 5) << 8) | (eb4 & 0xFF), c2b = eb4 & 0xFFFF, l_info = 1 + k;
-            const uint32_t l_size = lv + k + 2, c_size = (0x5320u >> (4 * e_t)) & 0xF;  // copies: 2, 3, 5 bytes
+            const uint32_t l_size = __builtin_elementwise_add_sat(lv, k + 2);
+            const uint32_t c_size = (0x5320u >> (4 * e_t)) & 0xF;  // copies: 2, 3, 5 bytes
             const bool is_l = e_t == 0, is_c1 = e_t == 1, is_c2 = e_t == 2;
             const uint32_t cx_olen = is_c1 ? c1_olen : c_olen;
             e_len = is_l ? l_olen : cx_olen;  // garbage lengths are clamped below
