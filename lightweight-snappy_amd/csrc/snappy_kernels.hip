@@ -3487,6 +3487,10 @@ __device__ __forceinline__ uint64_t rl64(uint64_t v, uint32_t l)
 constexpr uint32_t K5_IMG = K5_S + 128;
 [[maybe_unused]] constexpr uint32_t kK5Esc = 0xFFFFFFFFu;  // K5a entry map: no fast successor
 [[maybe_unused]] constexpr uint64_t kK5Esc64 = ~0ull;      // K5b1 block map: no fast successor
+// "parse failed" exit of a walk (relative in K5a, absolute in K5b2): a constant
+// above every stream position and every loop limit, so no subtraction of a
+// chunk start can bring it back below one
+[[maybe_unused]] constexpr uint64_t kK5Bad = 1ull << 62;
 
 // BYTES of stream from the 4-aligned absolute a0 into img (zero at and past clen)
 template <uint32_t BYTES>
@@ -3548,7 +3552,7 @@ __device__ __forceinline__ bool k5_parse_img(const uint32_t *img, uint32_t q, ui
 
 // Walk ONE element chain (x uniform, relative to c0) while x < end_rel (and,
 // MARK, op < N) by batch parse.  Not MARK (K5a): op accumulates the output, a
-// header past clen ends the walk with x = clen + 1 - c0.  MARK (K5c): op is
+// header past clen ends the walk with x = kK5Bad.  MARK (K5c): op is
 // the absolute output position; the checks and index entries of the serial
 // walk (an element holding a multiple of 65,536 strictly inside it gets a
 // straddle entry, one ending on it the entry of its successor); any error
@@ -3660,7 +3664,7 @@ __device__ __forceinline__ void k5_chain(const uint8_t *__restrict__ comp, uint3
         }
         if (er != SNAPPY_ST_OK) {
             if constexpr (MARK) st = er;
-            else x = clen + 1 - c0;  // a header past clen (the only error without MARK)
+            else x = kK5Bad;  // a header past clen (the only error without MARK)
         }
     }
 }
@@ -3678,7 +3682,16 @@ __global__ __launch_bounds__(64) void k5a_chunk_walk(const uint8_t *__restrict__
     const uint32_t c = blockIdx.x;
     const K5Hdr h = k5_header(comp, clen);
     const uint64_t c0 = h.len + (uint64_t)c * K5_S;
-    const uint32_t end_rel = (uint32_t)(c0 + K5_S < clen ? K5_S : clen - c0);
+    if (c0 >= clen) {
+        // the launch has ceil(clen / K5_S) chunks and the chunks start after the
+        // preamble, so the last one can start at or past clen: nothing to walk
+        // (K5b2 marks it K5_SKIP by E >= end and nothing looks it up)
+        X[(uint64_t)c * 64 + lane] = c0;
+        O[(uint64_t)c * 64 + lane] = 0;
+        P[(uint64_t)c * 64 + lane] = kK5Esc;
+        return;
+    }
+    const uint32_t end_rel = (uint32_t)(c0 + K5_S < clen ? K5_S : clen - c0);  // (c0 < clen)
     const uint32_t o0 = (uint32_t)(c0 & 3);
     k5_stage(comp, clen, c0, img, lane);
     uint64_t x = lane, cum = 0;
@@ -3689,7 +3702,7 @@ __global__ __launch_bounds__(64) void k5a_chunk_walk(const uint8_t *__restrict__
                 uint64_t size, len;
                 const uint32_t r = (uint32_t)x;
                 if (!k5_parse_img(img, r + o0, c0 + r < clen ? clen - (c0 + r) : 0, size, len)) {
-                    x = clen + 1 - c0;
+                    x = kK5Bad;
                 } else {
                     cum += len;
                     x += size;
@@ -3838,7 +3851,7 @@ __global__ __launch_bounds__(64) void k5b_carry(const uint8_t *__restrict__ comp
             while (x < end && base < N) {
                 uint64_t size, len;
                 if (!parse_la(x, size, len)) {
-                    x = clen + 1;
+                    x = kK5Bad;
                     break;
                 }
                 base += len;
@@ -3992,6 +4005,11 @@ __global__ __launch_bounds__(64) void k5c_mark(const uint8_t *__restrict__ comp,
             *fin = x;
         }
         if (st == SNAPPY_ST_OK && op < N && x >= clen) st = SNAPPY_ST_TRUNCATED;
+    } else if (c == 0 && lane == 0 && h.st == SNAPPY_ST_OK && h.N == 0 && max_units > 0) {
+        // an empty stream has no chunk whose walk reaches op == N: its one
+        // entry is the end of the preamble, as the serial K5 writes it
+        offsets[0] = h.len;
+        *fin = h.len;
     }
     if (lane == 0) cst[c] = st;
 }

@@ -17,7 +17,7 @@ from golden_inputs import build_stream, random_ops  # noqa: E402
 
 B = 65536
 S = 16384  # K5_S
-OK, TRUNC, OVERRUN, UNSUP = 0, -3, -5, -8
+OK, TRUNC, OVERRUN, UNSUP = 0, -3, -5, -9  # SNAPPY_ST_*
 
 
 def parse(s, x):
@@ -62,17 +62,24 @@ def serial(s, x, end, op, N, offs):
     return OK, x, op
 
 
-def batched(s, c0, x, end, op, N, offs):
-    """k5_chain<true> with x relative to c0, lanes as lists."""
+def batched(s, c0, x, end, op, N, offs, parse_at=None, win=0, ia=0, hook=None, skip_bits=24):
+    """k5_chain<true> with x relative to c0, lanes as lists.  parse_at(p): a
+    faster parse of the element at p (default parse(s, p)); win > 0: the image
+    is a window of win bytes from the 4-aligned ia, restaged at the chain when
+    the chain leaves it (K5c); hook(dict) sees every batch."""
     clen, st = len(s), OK
+    pa = parse_at or (lambda p: parse(s, p))
     while x < end - c0 and op < N and st == OK:
-        par = [parse(s, c0 + x + l) for l in range(64)]
-        size = [p[1] for p in par]
-        nxt = [l + min(size[l], 64) for l in range(64)]
-        pos, l0 = [], 0
-        while l0 < 64 and len(pos) < 32:  # = the pointer-doubling result
+        restaged = False
+        if win and c0 + x >= ia + win:
+            ia, restaged = (c0 + x) & ~3, True
+        assert not win or ia <= c0 + x < ia + win  # every read of the batch ends before ia + win + 72
+        # only the lanes on the chain from lane 0 matter (= the pointer-doubling result)
+        par, pos, l0 = {}, [], 0
+        while l0 < 64 and len(pos) < 32:
+            par[l0] = pa(c0 + x + l0)
             pos.append(l0)
-            l0 = nxt[l0]
+            l0 += min(par[l0][1], 64)
         pos = [p for p in pos if x + p < end - c0]
         E = len(pos)
         assert E >= 1
@@ -81,6 +88,7 @@ def batched(s, c0, x, end, op, N, offs):
         e_len = [par[p][2] for p in pos]
         e_x = [x + sum(e_size[:k]) for k in range(E)]
         e_op = [op + sum(e_len[:k]) for k in range(E)]
+        x0, wrote = x, []
         nexec, er = E, OK
         for k in range(E):
             bad = not e_ok[k] or c0 + e_x[k] + e_size[k] > clen
@@ -97,15 +105,20 @@ def batched(s, c0, x, end, op, N, offs):
             e_end = e_op[k] + e_len[k]
             if e_end % B == 0 and e_end < N:
                 offs[e_end // B] = c0 + e_x[k] + e_size[k]
+                wrote.append((k, "end"))
         for k in range(nexec):  # straddles, lane order
             nb, e_end, kx = (e_op[k] // B + 1) * B, e_op[k] + e_len[k], c0 + e_x[k]
             while nb < e_end and nb < N:
                 skip = nb - e_op[k]
-                if skip >> 24 or kx >> 40:
+                if skip >> skip_bits or kx >> 40:
                     er = UNSUP
                     break
                 offs[nb // B] = kx | (skip << 40)
+                wrote.append((k, "straddle"))
                 nb += B
+        if hook:
+            hook(dict(ia=ia, restaged=restaged, c0=c0, x=x0, e_x=e_x, e_size=e_size, e_len=e_len, e_op=e_op,
+                      nexec=nexec, er=er, wrote=wrote))
         if nexec:
             x = e_x[nexec - 1] + e_size[nexec - 1]
             op = e_op[nexec - 1] + e_len[nexec - 1]
