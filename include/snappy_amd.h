@@ -40,6 +40,7 @@ extern "C" {
 #define SNAPPY_AMD_ERR_UNSUPPORTED (-9)
 #define SNAPPY_AMD_ERR_TIMEOUT (-10)   /* a block waited too long for an earlier one  */
 #define SNAPPY_AMD_ERR_INDEX (-11)     /* a sidecar index that does not fit the stream */
+#define SNAPPY_AMD_ERR_CHECKSUM (-12)  /* a framed chunk's CRC-32C does not match its decoded bytes */
 
 /* Block size of the reference stream format (src/snappy_compression.c:9). */
 #define SNAPPY_AMD_BLOCK 65536u
@@ -227,6 +228,85 @@ int snappy_amd_decompress_device_ex(snappy_amd_ctx *ctx, const void *d_comp, con
  * bytes or covers a boundary more than 2^24 - 1 bytes after its start. */
 int snappy_amd_index_device(snappy_amd_ctx *ctx, const void *d_comp, size_t clen, uint64_t *d_offsets,
                             size_t max_units, size_t *n_out);
+
+/* ---- Snappy framing format (framing_format.txt of google/snappy) -------- */
+/* The file format other Snappy tools exchange: the 10-byte stream identifier
+ * ff 06 00 00 "sNaPpY", then chunks -- a type byte, a 24-bit little-endian
+ * length, and for data chunks the masked CRC-32C of the chunk's uncompressed
+ * bytes in front of the payload.  A data chunk holds at most 65,536
+ * uncompressed bytes, as its own raw Snappy stream (type 00) or stored (type
+ * 01).  The compressor here always writes type 00 chunks of 65,536 input
+ * bytes (the last one shorter), each payload equal to the SNAPPY_AMD_STREAMS
+ * unit of that piece, so the output is a pure function of the input.  The
+ * decoder takes what other writers emit: stored chunks, padding (fe) and
+ * skippable (80..fd) chunks, repeated identifiers, data chunks of any
+ * lengths.  Copies cannot reach outside their chunk (ERR_OFFSET).
+ *
+ * Chunk table (d_chunks, u64): entry i = byte position of data chunk i's
+ * header in the stream, entry nchunks = the stream length.  Compress returns
+ * it, decode takes it, frame_index_device builds it for a foreign stream.
+ *
+ * Errors of the framed decoders and walks.  Two stages, each reporting its
+ * first failing chunk: every chunk's header is checked before anything is
+ * decoded (ERR_HEADER, ERR_TRUNCATED, ERR_UNSUPPORTED, ERR_OVERRUN, ERR_INDEX,
+ * then ERR_CAPACITY), so a malformed header in a later chunk is reported ahead
+ * of an element or CRC error in an earlier one; among element and CRC errors
+ * the first failing chunk wins, and a CRC is checked only where the chunk's
+ * decode succeeded:
+ *   ERR_HEADER       no or a wrong stream identifier, a later ff chunk that is
+ *                    not the identifier, a data chunk shorter than its CRC,
+ *                    an unreadable preamble in a compressed chunk
+ *   ERR_TRUNCATED    a chunk (or its header) runs past the end
+ *   ERR_UNSUPPORTED  a reserved unskippable chunk, types 02..7f
+ *   ERR_OVERRUN      a data chunk that decodes to more than 65,536 bytes
+ *   ERR_CAPACITY     output (or chunk table) too small; before any decode
+ *   ERR_INDEX        a chunk table entry that is not a data chunk's header
+ *   ERR_CHECKSUM     CRC mismatch;  element errors as the decoder reports them */
+#define SNAPPY_AMD_FRAME_NO_IDENTIFIER 1u /* this buffer continues a framed stream */
+
+/* CRC-32C (polynomial 0x82F63B78 reflected, init and xor-out ffffffff) of
+ * `count` byte ranges of d_base: d_off_len holds (offset, length) pairs, any
+ * alignment, d_crc gets one u32 each -- masked != 0: the framing format's
+ * ((c >> 15) | (c << 17)) + 0xa282ead8.  Asynchronous on the context stream. */
+int snappy_amd_crc32c_device(snappy_amd_ctx *ctx, const void *d_base, const uint64_t *d_off_len, size_t count,
+                             int masked, uint32_t *d_crc);
+/* Capacity d_out must have for compress_frame_device:
+ * 10 + 8 ceil(n / 65536) + snappy_amd_max_output(n, 65536, SNAPPY_AMD_STREAMS). */
+size_t snappy_amd_max_frame_output(size_t n);
+/* Frame d_in[0..n): identifier (unless SNAPPY_AMD_FRAME_NO_IDENTIFIER), then
+ * ceil(n / 65536) compressed chunks.  d_chunks receives ceil(n / 65536) + 1
+ * entries.  n == 0 writes the identifier alone. */
+int snappy_amd_compress_frame_device(snappy_amd_ctx *ctx, const void *d_in, size_t n, uint32_t flags, void *d_out,
+                                     uint64_t *d_chunks, size_t *out_len);
+/* Walk a framed stream in HBM from its identifier: d_chunks (room for
+ * max_chunks entries, the closing one included) gets the chunk table,
+ * *nchunks_out the data chunks, *n_out the decoded bytes.  One wave follows
+ * the headers, one dependent step per chunk.  The stream must begin with the
+ * identifier: a continuation piece (SNAPPY_AMD_FRAME_NO_IDENTIFIER) is not
+ * indexed on its own -- keep the table its compress call returned. */
+int snappy_amd_frame_index_device(snappy_amd_ctx *ctx, const void *d_frame, size_t clen, uint64_t *d_chunks,
+                                  size_t max_chunks, size_t *nchunks_out, size_t *n_out);
+/* Decode the data chunks a chunk table names into d_out (cap bytes) and check
+ * their CRCs; *n_out = decoded bytes.  Every table entry is checked against
+ * clen; that the table is complete is the caller's word. */
+int snappy_amd_decompress_frame_device(snappy_amd_ctx *ctx, const void *d_frame, size_t clen,
+                                       const uint64_t *d_chunks, size_t nchunks, void *d_out, size_t cap,
+                                       size_t *n_out);
+/* (snappy_amd_last_timings covers the unframed calls only: the framed ones
+ * record no events.) */
+/* Host memory: out must hold snappy_amd_max_frame_output(n).  Inputs of more
+ * than 64 MiB go piece by piece (SNAPPY_AMD_FRAME_PIECE_KB, a multiple of 64,
+ * sets another piece size for the buffer and FILE* compressors and the FILE*
+ * decoder's read buffer; the bytes written do not depend on it). */
+int snappy_compress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len);
+int snappy_decompress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len);
+/* Decoded bytes of a framed stream: the chunk walk on the host (no kernel),
+ * the same rules as frame_index_device. */
+int snappy_frame_uncompressed_length(const uint8_t *in, size_t n, uint64_t *len);
+/* FILE* forms: file_input from its current position to EOF (input_size is
+ * not needed: the format stores no total length). */
+int snappy_compress_file_framed(FILE *file_input, unsigned long long input_size, FILE *file_compressed);
+int snappy_decompress_file_framed(FILE *file_input, FILE *file_decompressed);
 
 /* Kernel timing of the last compress/decompress call, measured with HIP
  * events on the launch stream: K1 (block compress), K3 (scan + gather),

@@ -6,6 +6,9 @@
  * -i (an addition): with -c also write the sidecar block
  * index <outfile>.idx; with -d decode with <infile>.idx instead of the GPU
  * index pass.
+ * -f (an addition): with -c write, with -d read the Snappy framing format
+ * (framing_format.txt of google/snappy), the file format of other Snappy
+ * tools; not with -b or -i.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -19,12 +22,13 @@
 static void usage(void)
 {
     fprintf(stderr,
-            "snappy [-c|-d|-b] [-r] [-i] [infile] [outfile]\n"
+            "snappy [-c|-d|-b] [-r] [-i] [-f] [infile] [outfile]\n"
             "-c compress (MI355X)\n"
-            "-b compress with the BST matcher (not supported on MI355X)\n"
+            "-b compress with the BST matcher\n"
             "-d decompress (MI355X)\n"
             "-r print results\n"
-            "-i -c: also write outfile.idx (block index); -d: use infile.idx\n");
+            "-i -c: also write outfile.idx (block index); -d: use infile.idx\n"
+            "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -49,17 +53,19 @@ static unsigned long long file_size(FILE *f)
 int main(int argc, char *argv[])
 {
     enum { M_COMPRESS, M_BST, M_DECOMPRESS } mode = M_COMPRESS;
-    int show = 0, indexed = 0, opt;
+    int show = 0, indexed = 0, framed = 0, opt;
     if (argc < 4) usage();
-    while ((opt = getopt(argc, argv, "cbdri")) != -1) {
+    while ((opt = getopt(argc, argv, "cbdrif")) != -1) {
         if (opt == 'c') mode = M_COMPRESS;
         else if (opt == 'b') mode = M_BST;
         else if (opt == 'd') mode = M_DECOMPRESS;
         else if (opt == 'r') show = 1;
         else if (opt == 'i') indexed = 1;
+        else if (opt == 'f') framed = 1;
         else usage();
     }
     if (indexed && mode == M_BST) usage();  /* -b writes no block index */
+    if (framed && (indexed || mode == M_BST)) usage();  /* a framed stream has its chunk headers; -b is unframed */
     const char *in_name = argv[argc - 2], *out_name = argv[argc - 1];
     FILE *in = open_or_die(in_name, "rb");
     FILE *out = open_or_die(out_name, "wb");
@@ -74,7 +80,9 @@ int main(int argc, char *argv[])
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     int rc = 0;
-    if (mode == M_COMPRESS && idx) {
+    if (framed) {
+        rc = mode == M_COMPRESS ? snappy_compress_file_framed(in, in_size, out) : snappy_decompress_file_framed(in, out);
+    } else if (mode == M_COMPRESS && idx) {
         rc = snappy_compress_file_indexed(in, in_size, out, idx);
     } else if (mode == M_COMPRESS) {
         snappy_compress(in, in_size, out);

@@ -38,6 +38,10 @@ struct snappy_amd_ctx {
     uint64_t *d_idx = nullptr; size_t d_idx_cap = 0;
     uint8_t *k5buf = nullptr; size_t k5buf_cap = 0;  // chunk-parallel index scratch
     uint8_t *k5copy = nullptr; size_t k5copy_cap = 0;  // aligned copy of a misaligned stream
+    // framing format (snappy_frame.hip): tables of a framed call (scan offsets, CRCs,
+    // chunk records, unit index, status words) and the unframed payloads K4 decodes
+    uint8_t *f_meta = nullptr; size_t f_meta_cap = 0;
+    uint8_t *f_scr = nullptr; size_t f_scr_cap = 0;
     bool timing = false;
     bool serial_index = false;  // SNAPPY_AMD_OPT_SERIAL_INDEX
     uint32_t k1r_extra_lds = 0; // SNAPPY_AMD_OPT_K1R_EXTRA_LDS
@@ -56,6 +60,11 @@ SNAPPY_PRIVATE int grow(void **ptr, size_t *cap, size_t need);
 // c->stream, creating the context's own stream if none is bound and none was
 // made yet (contexts create it lazily: a caller-bound stream leaves no idle one)
 SNAPPY_PRIVATE int ctx_stream(snappy_amd_ctx *c);
+// lease a pooled host context of the calling thread's device, as the host-buffer
+// and FILE* calls do (snappy_pipeline.cpp); *ctx = its device context, already on
+// its own stream.  host_ctx_return gives it back to the pool.
+extern "C" SNAPPY_PRIVATE int host_ctx_lease(void **token, snappy_amd_ctx **ctx);
+extern "C" SNAPPY_PRIVATE void host_ctx_return(void *token);
 // K1r (or K1r64) -> K3 -> K2 on c->stream; *out_len (when non-null) after a
 // sync of that stream, otherwise the size stays in c->total (device)
 extern "C" SNAPPY_PRIVATE int compress_impl(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk, int layout,

@@ -90,7 +90,7 @@ void snappy_amd_destroy(snappy_amd_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->sizes, c->tokens, c->ntok, c->seg_off, c->status, c->total, c->k5res,
-                    c->d_a, c->d_b, c->d_idx, c->k5buf, c->k5copy};
+                    c->d_a, c->d_b, c->d_idx, c->k5buf, c->k5copy, c->f_meta, c->f_scr};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->h_total) (void)hipHostFree(c->h_total);
     if (c->h_status) (void)hipHostFree(c->h_status);
@@ -103,7 +103,7 @@ size_t snappy_amd_device_bytes(snappy_amd_ctx *c)
 {
     if (!c) return 0;
     return c->sizes_cap + c->tokens_cap + c->ntok_cap + c->seg_off_cap + c->status_cap + c->d_a_cap + c->d_b_cap +
-           c->d_idx_cap + c->k5buf_cap + c->k5copy_cap + 128;
+           c->d_idx_cap + c->k5buf_cap + c->k5copy_cap + c->f_meta_cap + c->f_scr_cap + 128;
 }
 
 int snappy_amd_trim(snappy_amd_ctx *c)
@@ -117,6 +117,7 @@ int snappy_amd_trim(snappy_amd_ctx *c)
         {reinterpret_cast<void **>(&c->d_a), &c->d_a_cap}, {reinterpret_cast<void **>(&c->d_b), &c->d_b_cap},
         {reinterpret_cast<void **>(&c->d_idx), &c->d_idx_cap}, {reinterpret_cast<void **>(&c->k5buf), &c->k5buf_cap},
         {reinterpret_cast<void **>(&c->k5copy), &c->k5copy_cap},
+        {reinterpret_cast<void **>(&c->f_meta), &c->f_meta_cap}, {reinterpret_cast<void **>(&c->f_scr), &c->f_scr_cap},
         // a decode's status words only once its status has been read (the result is kept)
         {reinterpret_cast<void **>(&c->status), c->status_pending ? nullptr : &c->status_cap}};
     for (auto &b : bufs) {
@@ -221,6 +222,9 @@ int compress_impl(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk,
     }
     const size_t units = (n + unit - 1) / unit;
     int rc;
+    // (snappy_amd_compress_frame_device, snappy_frame.hip, repeats the scratch sizing and the
+    // K1r64 / K3 / K2 launches below for units of 65,536 with a kernel of its own between
+    // K1r64 and K3: a change to either here has to be made there too)
     // register-resident match finder -> tokens; scan; emit in place
     const uint32_t tok_cap = unit / 4 + 2;
     if ((rc = grow(reinterpret_cast<void **>(&c->tokens), &c->tokens_cap,

@@ -633,6 +633,23 @@ int sidecar_verdict(snappy_amd_ctx *c, const uint8_t *d_stream, size_t n, const 
 bool length_plausible(uint64_t N, uint64_t n) { return N / 22 <= n; }
 }  // namespace
 
+// the pool for host code outside this file (snappy_frame_host.cpp)
+int host_ctx_lease(void **token, snappy_amd_ctx **ctx)
+{
+    Lease *l = new (std::nothrow) Lease(host_device());
+    if (!l) return SNAPPY_AMD_ERR_DEVICE;
+    if (l->rc()) {
+        const int rc = l->rc();
+        delete l;
+        return rc;
+    }
+    *token = l;
+    *ctx = (*l)->c;
+    return SNAPPY_AMD_OK;
+}
+
+void host_ctx_return(void *token) { delete static_cast<Lease *>(token); }
+
 int snappy_amd_host_set_device(int device)
 {
     int count = 0;

@@ -35,6 +35,9 @@ ERR_IO = -8
 ERR_UNSUPPORTED = -9
 ERR_TIMEOUT = -10
 ERR_INDEX = -11
+ERR_CHECKSUM = -12
+FRAME_NO_IDENTIFIER = 1  # compress_frame_*: this buffer continues a framed stream
+FRAME_IDENTIFIER = bytes.fromhex("ff060000734e61507059")
 IDX_MAGIC = 0x3158444941504E53  # b"SNPAIDX1" as a little-endian u64
 
 BLOCK = 65536
@@ -56,6 +59,7 @@ _NAMES = {
     ERR_UNSUPPORTED: "unsupported",
     ERR_TIMEOUT: "block dependency wait timed out",
     ERR_INDEX: "sidecar index does not fit the stream",
+    ERR_CHECKSUM: "chunk CRC-32C mismatch",
 }
 
 # every function include/*.h declares, with its ctypes signature
@@ -123,6 +127,24 @@ _SIGS = {
                                                  _c.POINTER(_c.c_uint64)]),
     # FILE* in, sidecar entries (or NULL) and their count, FILE* out
     "snappy_amd_host_decompress_file": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    # framing format
+    "snappy_amd_crc32c_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                            _c.c_void_p]),
+    "snappy_amd_max_frame_output": (_c.c_size_t, [_c.c_size_t]),
+    "snappy_amd_compress_frame_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_void_p,
+                                                    _c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_frame_index_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                 _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_decompress_frame_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                      _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                      _c.POINTER(_c.c_size_t)]),
+    "snappy_compress_frame_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                _c.POINTER(_c.c_size_t)]),
+    "snappy_decompress_frame_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                  _c.POINTER(_c.c_size_t)]),
+    "snappy_frame_uncompressed_length": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint64)]),
+    "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
+    "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
 }
 # the reference Buffer cursor helpers, in libsnappy_amd_compat.so (Buffer* is a
 # struct of two pointers and a u32)
@@ -284,6 +306,40 @@ def decompress_multi(data, devices) -> bytes:
     got = ctypes.c_size_t(0)
     _check(lib().snappy_decompress_buffer_multi(devs, len(devices), p, n, out, N, ctypes.byref(got)),
            "decompress_multi")
+    return out.raw[: got.value]
+
+
+def max_frame_output(n: int) -> int:
+    return lib().snappy_amd_max_frame_output(n)
+
+
+def compress_frame(data) -> bytes:
+    """data in the Snappy framing format (framing_format.txt): the stream
+    identifier, then one compressed chunk with its CRC-32C per 65,536 bytes."""
+    p, n, keep = _buf(data)
+    cap = max_frame_output(n)
+    out = ctypes.create_string_buffer(cap)
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_compress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "compress_frame")
+    return out.raw[: got.value]
+
+
+def frame_uncompressed_length(data) -> int:
+    """Decoded bytes of a framed stream (the chunk walk on the host, no GPU)."""
+    p, n, keep = _buf(data)
+    v = ctypes.c_uint64(0)
+    _check(lib().snappy_frame_uncompressed_length(p, n, ctypes.byref(v)), "frame_uncompressed_length")
+    return v.value
+
+
+def decompress_frame(data, cap: Optional[int] = None) -> bytes:
+    """Decode a framed stream of any writer, checking every chunk's CRC-32C."""
+    p, n, keep = _buf(data)
+    if cap is None:
+        cap = frame_uncompressed_length(data)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_decompress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "decompress_frame")
     return out.raw[: got.value]
 
 
@@ -464,3 +520,62 @@ class Codec:
         n = self.index_ptr(comp.data_ptr(), comp.numel(), offs.data_ptr(), units_max + 1)
         units = (n + BLOCK - 1) // BLOCK
         return n, offs[: units + 1]
+
+    # framing format ----------------------------------------------------------
+    def crc32c_tensor(self, base, off_len, masked: bool = False):
+        """CRC-32C of byte ranges of `base` (uint8 CUDA tensor): off_len is an
+        int64 CUDA tensor of (offset, length) pairs -> int32 tensor of u32 bits."""
+        assert base.is_cuda and base.dtype == torch.uint8 and off_len.is_cuda and off_len.dtype == torch.int64
+        count = off_len.numel() // 2
+        out = torch.empty(max(count, 1), dtype=torch.int32, device=base.device)
+        self._bind_stream()
+        _check(lib().snappy_amd_crc32c_device(self._h, ctypes.c_void_p(base.data_ptr()),
+                                              ctypes.c_void_p(off_len.data_ptr()), count, 1 if masked else 0,
+                                              ctypes.c_void_p(out.data_ptr())), "crc32c_device")
+        return out[:count]
+
+    def compress_frame_ptr(self, d_in: int, n: int, flags: int, d_out: int, d_chunks: int) -> int:
+        got = ctypes.c_size_t(0)
+        _check(lib().snappy_amd_compress_frame_device(self._h, ctypes.c_void_p(d_in), n, flags, ctypes.c_void_p(d_out),
+                                                      ctypes.c_void_p(d_chunks), ctypes.byref(got)),
+               "compress_frame_device")
+        return got.value
+
+    def compress_frame_tensor(self, x, flags: int = 0):
+        """x: contiguous uint8 CUDA tensor -> (framed stream tensor, chunk table tensor)."""
+        assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        n = x.numel()
+        out = torch.empty(max_frame_output(n), dtype=torch.uint8, device=x.device)
+        chunks = torch.empty((n + BLOCK - 1) // BLOCK + 1, dtype=torch.int64, device=x.device)
+        self._bind_stream()
+        length = self.compress_frame_ptr(x.data_ptr(), n, flags, out.data_ptr(), chunks.data_ptr())
+        return out[:length], chunks
+
+    def frame_index_tensor(self, frame, max_chunks: Optional[int] = None):
+        """Chunk table of a framed stream in HBM -> (decoded bytes, table tensor
+        of data chunks + 1 entries).  A stream holds at most one data chunk per
+        8 bytes, which bounds the table when max_chunks is not given."""
+        assert frame.is_cuda and frame.dtype == torch.uint8 and frame.is_contiguous()
+        if max_chunks is None:
+            max_chunks = frame.numel() // 8 + 2
+        chunks = torch.empty(max(max_chunks, 1), dtype=torch.int64, device=frame.device)
+        nch, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_frame_index_device(self._h, ctypes.c_void_p(frame.data_ptr()), frame.numel(),
+                                                   ctypes.c_void_p(chunks.data_ptr()), max_chunks, ctypes.byref(nch),
+                                                   ctypes.byref(n)), "frame_index_device")
+        return n.value, chunks[: nch.value + 1]
+
+    def decompress_frame_tensor(self, frame, chunks, n: int, out=None):
+        """Decode the data chunks `chunks` names (compress_frame_tensor's or
+        frame_index_tensor's table) into n bytes; raises on a CRC mismatch."""
+        assert frame.is_cuda and frame.dtype == torch.uint8 and chunks.dtype == torch.int64
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.uint8, device=frame.device)
+        got = ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_decompress_frame_device(self._h, ctypes.c_void_p(frame.data_ptr()), frame.numel(),
+                                                        ctypes.c_void_p(chunks.data_ptr()), chunks.numel() - 1,
+                                                        ctypes.c_void_p(out.data_ptr()), n, ctypes.byref(got)),
+               "decompress_frame_device")
+        return out[: got.value]

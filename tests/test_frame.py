@@ -1,0 +1,451 @@
+"""GPU: the Snappy framing format -- KF1 (batched CRC-32C), framed compress
+(bit for bit the model's framing of the oracle's 65,536-byte streams), framed
+decode of this library's and of foreign streams (every chunk type, runs of
+unequal chunks), and the error table.  Conformance rests on the model in
+tests/frame_model.py, pinned to published values by test_frame_model.py."""
+import functools
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+import datagen
+import frame_model as fm
+import oracle
+import snappy_amd
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "lightweight-snappy_amd", "snappy")
+CH = 65536
+SENT = 0xA5
+
+
+def dev(b) -> torch.Tensor:
+    return torch.from_numpy(np.frombuffer(bytes(b), dtype=np.uint8).copy()).cuda() if len(b) else \
+        torch.empty(0, dtype=torch.uint8, device="cuda")
+
+
+def host(t) -> bytes:
+    return t.cpu().numpy().tobytes()
+
+
+# ---- KF1 --------------------------------------------------------------------
+LENGTHS = [0, 1, 2, 3, 4, 5, 7, 8, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 65535, 65536]
+PUBLISHED = [b"123456789", bytes(32), b"\xff" * 32, bytes(range(32)), bytes(range(31, -1, -1))]
+
+
+@functools.lru_cache(maxsize=None)
+def crc_entries(kind):
+    """Adjacent entries of every length (then the published vectors) filled
+    with one kind of data, and their model CRCs."""
+    total = sum(LENGTHS)
+    if kind == "zeros":
+        body = bytes(total)
+    elif kind == "ff":
+        body = b"\xff" * total
+    elif kind == "inc":
+        body = bytes(i & 0xFF for i in range(total))
+    else:
+        body = datagen.make("R", total, 99).tobytes()
+    ents, at = [], 0
+    for n in LENGTHS:
+        ents.append(body[at:at + n])
+        at += n
+    ents += PUBLISHED
+    return ents, [fm.crc32c(e) for e in ents]
+
+
+@pytest.mark.parametrize("kind", ["zeros", "ff", "inc", "noise"])
+def test_kf1_crc32c_every_length_and_alignment(codec, kind):
+    ents, want = crc_entries(kind)
+    blob = b"".join(ents)
+    for align in range(8):
+        # the entries lie back to back from `align` on: a read past an entry's end
+        # (or before its start) takes its neighbour's bytes and changes the value
+        buf = dev(b"\x5a" * align + blob + b"\x5a" * 8)
+        tab, at = [], align
+        for e in ents:
+            tab += [at, len(e)]
+            at += len(e)
+        ol = torch.tensor(tab, dtype=torch.int64, device="cuda")
+        raw = codec.crc32c_tensor(buf, ol, masked=False).cpu().numpy().view(np.uint32).tolist()
+        msk = codec.crc32c_tensor(buf, ol, masked=True).cpu().numpy().view(np.uint32).tolist()
+        for i, e in enumerate(ents):
+            assert raw[i] == want[i], (kind, align, len(e), hex(raw[i]), hex(want[i]))
+            assert msk[i] == fm.mask(want[i]), (kind, align, len(e))
+
+
+def test_kf1_published_vectors(codec):
+    vec = [(b"123456789", 0xE3069283), (bytes(32), 0x8A9136AA), (b"\xff" * 32, 0x62A8AB43),
+           (bytes(range(32)), 0x46DD794E), (bytes(range(31, -1, -1)), 0x113FDB5C), (b"", 0), (b"a", 0xC1D04330)]
+    buf = dev(b"".join(v for v, _ in vec))
+    tab, at = [], 0
+    for v, _ in vec:
+        tab += [at, len(v)]
+        at += len(v)
+    got = codec.crc32c_tensor(buf, torch.tensor(tab, dtype=torch.int64, device="cuda")).cpu().numpy().view(np.uint32)
+    assert got.tolist() == [c for _, c in vec]
+    m = codec.crc32c_tensor(buf, torch.tensor(tab, dtype=torch.int64, device="cuda"), masked=True)
+    assert m.cpu().numpy().view(np.uint32).tolist()[0] == 0xC78AB0E5
+
+
+# ---- compress ---------------------------------------------------------------
+SIZES = [0, 1, 65535, 65536, 65537, 5 * 65536 + 17]
+CASES = [(k, n) for k in "TR" for n in SIZES]
+
+
+@functools.lru_cache(maxsize=None)
+def case(kind, n):
+    """input array, the model's framing of the oracle's streams, its chunk table"""
+    a = datagen.make(kind, n, 4321)
+    if n:
+        payload, offs = oracle.compress_streams(a, CH)
+        want = fm.frame_streams(a.tobytes(), payload.tobytes(), offs)
+    else:
+        want = fm.IDENTIFIER
+    st, table, total = fm.chunk_table(want)
+    assert st == fm.OK and total == n
+    return a, want, table
+
+
+@pytest.mark.parametrize("kind,n", CASES)
+def test_compress_frame_device_bit_for_bit(codec, kind, n):
+    a, want, table = case(kind, n)
+    x = dev(a.tobytes())
+    frame, chunks = codec.compress_frame_tensor(x)
+    assert frame.numel() <= snappy_amd.max_frame_output(n)
+    assert host(frame) == want
+    assert chunks.cpu().tolist() == table
+    # NO_IDENTIFIER drops exactly the first 10 bytes (and moves the table by 10)
+    frame2, chunks2 = codec.compress_frame_tensor(x, flags=snappy_amd.FRAME_NO_IDENTIFIER)
+    assert host(frame2) == want[10:]
+    assert chunks2.cpu().tolist() == [t - 10 for t in table]
+
+
+@pytest.mark.parametrize("kind,n", [("T", 5 * 65536 + 17), ("R", 65537), ("T", 1), ("T", 0)])
+def test_compress_frame_output_alignment_and_sentinel(codec, kind, n):
+    a, want, table = case(kind, n)
+    x = dev(a.tobytes())
+    cap = snappy_amd.max_frame_output(n)
+    for align in range(4):
+        buf = torch.full((cap + 64,), SENT, dtype=torch.uint8, device="cuda")
+        chunks = torch.empty(len(table), dtype=torch.int64, device="cuda")
+        codec._bind_stream()
+        got = codec.compress_frame_ptr(x.data_ptr() if n else 0, n, 0, buf.data_ptr() + align, chunks.data_ptr())
+        assert got == len(want) <= cap
+        b = host(buf)
+        assert b[align:align + got] == want
+        assert b[:align] == bytes([SENT]) * align and b[align + got:] == bytes([SENT]) * (len(b) - align - got)
+        assert chunks.cpu().tolist() == table
+
+
+@pytest.mark.parametrize("kind,n", CASES)
+def test_compress_frame_host_buffer(kind, n):
+    a, want, _ = case(kind, n)
+    assert snappy_amd.compress_frame(a.tobytes()) == want
+
+
+# ---- decode, own streams ----------------------------------------------------
+@pytest.mark.parametrize("kind,n", CASES)
+def test_round_trip_device_and_buffer(codec, kind, n):
+    a, want, table = case(kind, n)
+    frame = dev(want)
+    chunks = torch.tensor(table, dtype=torch.int64, device="cuda")
+    back = codec.decompress_frame_tensor(frame, chunks, n)
+    assert host(back) == a.tobytes()
+    assert snappy_amd.decompress_frame(want) == a.tobytes()
+    # the stream without its identifier, as a continuation piece's table describes it
+    if n:
+        cont = codec.decompress_frame_tensor(dev(want[10:]), torch.tensor([t - 10 for t in table], dtype=torch.int64,
+                                                                          device="cuda"), n)
+        assert host(cont) == a.tobytes()
+
+
+def _cli_round_trip(a, want, env=None):
+    """snappy -f -c / -f -d (snappy_compress_file_framed, snappy_decompress_file_framed) in a temp dir"""
+    with tempfile.TemporaryDirectory() as d:
+        src, snp, dec = (os.path.join(d, x) for x in ("in", "in.sz", "in.dec"))
+        open(src, "wb").write(a)
+        subprocess.run([EXE, "-f", "-c", src, snp], check=True, capture_output=True, env=env)
+        assert open(snp, "rb").read() == want
+        subprocess.run([EXE, "-f", "-d", snp, dec], check=True, capture_output=True, env=env)
+        assert open(dec, "rb").read() == a
+
+
+@pytest.mark.parametrize("kind,n", CASES)
+def test_cli_framed_round_trip(kind, n):
+    a, want, _ = case(kind, n)
+    _cli_round_trip(a.tobytes(), want)
+
+
+def test_cli_framed_goes_with_c_and_d_only(tmp_path):
+    src, snp = str(tmp_path / "in"), str(tmp_path / "out")
+    open(src, "wb").write(b"x")
+    for flags in (["-f", "-b"], ["-f", "-c", "-i"], ["-f", "-d", "-i"]):
+        r = subprocess.run([EXE] + flags + [src, snp], capture_output=True)
+        assert r.returncode == 1 and b"snappy [-c|-d|-b]" in r.stderr
+
+
+# ---- more than one piece ------------------------------------------------------
+# The buffer and FILE* forms take 64 MiB at a time; SNAPPY_AMD_FRAME_PIECE_KB
+# makes the pieces small enough for these inputs to cross them.
+@pytest.mark.parametrize("piece_kb", [64, 128])
+def test_pieces_compress_buffer_continues_without_identifier(monkeypatch, piece_kb):
+    a, want, _ = case("T", 5 * 65536 + 17)  # 6 chunks: 6 or 3 pieces
+    monkeypatch.setenv("SNAPPY_AMD_FRAME_PIECE_KB", str(piece_kb))
+    assert snappy_amd.compress_frame(a.tobytes()) == want
+
+
+@pytest.mark.parametrize("piece_kb", [64, 128])
+def test_pieces_file_forms_cut_at_chunk_boundaries(piece_kb):
+    env = dict(os.environ, SNAPPY_AMD_FRAME_PIECE_KB=str(piece_kb))
+    a, want, _ = case("T", 5 * 65536 + 17)
+    _cli_round_trip(a.tobytes(), want, env)  # text: reads end inside compressed chunks
+    a, want, _ = case("R", 5 * 65536 + 17)
+    _cli_round_trip(a.tobytes(), want, env)  # random: every chunk is larger than a 64 KiB read
+    # a foreign stream: chunks of unequal sizes, padding and a repeated identifier across the cuts
+    for name in ("three runs", "padding of 0 and of 7 bytes", "identifier repeated mid-stream and at the end"):
+        stream, raw = FOREIGN[name]()
+        with tempfile.TemporaryDirectory() as d:
+            snp, dec = os.path.join(d, "in.sz"), os.path.join(d, "in.dec")
+            open(snp, "wb").write(stream)
+            subprocess.run([EXE, "-f", "-d", snp, dec], check=True, capture_output=True, env=env)
+            assert open(dec, "rb").read() == raw
+
+
+def test_pieces_file_decode_reports_a_cut_stream():
+    env = dict(os.environ, SNAPPY_AMD_FRAME_PIECE_KB="64")
+    _, want, _ = case("T", 5 * 65536 + 17)
+    with tempfile.TemporaryDirectory() as d:
+        snp, dec = os.path.join(d, "in.sz"), os.path.join(d, "in.dec")
+        open(snp, "wb").write(want[:-1])
+        r = subprocess.run([EXE, "-f", "-d", snp, dec], capture_output=True, env=env)
+        assert r.returncode == 1
+
+
+# ---- decode, foreign streams --------------------------------------------------
+def pieces(sizes, kind="T", seed=11):
+    a = datagen.make(kind, max(sum(sizes), 1), seed).tobytes()
+    out, at = [], 0
+    for s in sizes:
+        out.append(a[at:at + s])
+        at += s
+    return out
+
+
+def comp(raw):
+    return fm.compressed(raw, oracle.compress(raw) if raw else fm.varint(0))
+
+
+def _mixed():
+    p = pieces([65536, 1000, 65536, 17])
+    return fm.IDENTIFIER + comp(p[0]) + fm.stored(p[1]) + fm.stored(p[2]) + comp(p[3]), b"".join(p)
+
+
+def _padding():
+    p = pieces([5000, 5000, 300])
+    return fm.IDENTIFIER + comp(p[0]) + fm.padding(0) + comp(p[1]) + fm.padding(7) + fm.stored(p[2]), b"".join(p)
+
+
+def _skippable():
+    p = pieces([4096, 4096])
+    return fm.IDENTIFIER + fm.skippable(0x80, b"index: none") + comp(p[0]) + fm.skippable(0xFD, b"") + comp(p[1]), \
+        b"".join(p)
+
+
+def _identifiers():
+    p = pieces([70, 65536])
+    return fm.IDENTIFIER + comp(p[0]) + fm.IDENTIFIER + comp(p[1]) + fm.IDENTIFIER, b"".join(p)
+
+
+def _seq(sizes, kind="T"):
+    p = pieces(sizes, kind)
+    return fm.IDENTIFIER + b"".join(comp(x) for x in p), b"".join(p)
+
+
+FOREIGN = {
+    "stored chunks of 1 byte": lambda: (fm.IDENTIFIER + b"".join(fm.stored(x) for x in pieces([1] * 5)),
+                                        b"".join(pieces([1] * 5))),
+    "stored chunks of 65,536 bytes": lambda: (fm.IDENTIFIER + b"".join(fm.stored(x) for x in pieces([CH] * 3, "R")),
+                                              b"".join(pieces([CH] * 3, "R"))),
+    "stored chunks at the literal-tag edges": lambda: (
+        fm.IDENTIFIER + b"".join(fm.stored(x) for x in pieces([60, 61, 256, 257, 127, 128, 16383, 16384])),
+        b"".join(pieces([60, 61, 256, 257, 127, 128, 16383, 16384]))),
+    "compressed and stored mixed": _mixed,
+    "padding of 0 and of 7 bytes": _padding,
+    "skippable chunks": _skippable,
+    "identifier repeated mid-stream and at the end": _identifiers,
+    "uniform chunks of 4,096": lambda: _seq([4096] * 9 + [123]),
+    "three runs": lambda: _seq([65536, 100, 65536, 65536, 1, 40000]),
+    "rising sizes (a run each)": lambda: _seq([1, 2, 3, 700, 65536]),
+    "data chunks that all decode to 0 bytes": lambda: (fm.IDENTIFIER + comp(b"") + fm.stored(b"") + comp(b""), b""),
+    "empty chunks between full ones": lambda: (
+        fm.IDENTIFIER + comp(pieces([300])[0]) + fm.stored(b"") + comp(b"") + comp(pieces([300])[0]),
+        pieces([300])[0] * 2),
+}
+
+
+@pytest.mark.parametrize("name", list(FOREIGN))
+def test_decode_foreign_stream(codec, name):
+    stream, want = FOREIGN[name]()
+    st, table, total = fm.chunk_table(stream)
+    assert st == fm.OK and total == len(want)
+    assert fm.read(stream, oracle.decompress) == want  # the model reads its own stream
+    # host walk + buffer decode
+    assert snappy_amd.frame_uncompressed_length(stream) == len(want)
+    assert snappy_amd.decompress_frame(stream) == want
+    # device walk == host walk, then the device decode with that table
+    frame = dev(stream)
+    n, chunks = codec.frame_index_tensor(frame)
+    assert n == len(want) and chunks.cpu().tolist() == table
+    assert host(codec.decompress_frame_tensor(frame, chunks, n)) == want
+
+
+def test_device_walk_follows_the_host_walk_on_mutated_streams(codec):
+    """KF3 and the host walk share their chunk rules; both must give the
+    model's status, total and table on streams with a byte changed or a cut."""
+    from test_frame_model import mutated_streams
+    for stream, st, total in mutated_streams(150, 77):
+        want_table = fm.chunk_table(stream)[1]
+        try:
+            n, chunks = codec.frame_index_tensor(dev(stream))
+            rc = 0
+        except snappy_amd.SnappyError as e:
+            rc = e.code
+        assert rc == st, (stream.hex(), rc, st)
+        if st == fm.OK:
+            assert n == total and chunks.cpu().tolist() == want_table
+            assert snappy_amd.frame_uncompressed_length(stream) == total
+
+
+def test_frame_index_capacity(codec):
+    stream, want = FOREIGN["uniform chunks of 4,096"]()
+    table = fm.chunk_table(stream)[1]
+    frame = dev(stream)
+    n, chunks = codec.frame_index_tensor(frame, max_chunks=len(table))  # data chunks + the closing entry
+    assert n == len(want) and chunks.cpu().tolist() == table
+    with pytest.raises(snappy_amd.SnappyError) as e:
+        codec.frame_index_tensor(frame, max_chunks=len(table) - 1)
+    assert e.value.code == snappy_amd.ERR_CAPACITY
+
+
+def test_decode_foreign_stream_file_form():
+    stream, want = FOREIGN["three runs"]()
+    with tempfile.TemporaryDirectory() as d:
+        snp, dec = os.path.join(d, "in.sz"), os.path.join(d, "in.dec")
+        open(snp, "wb").write(stream)
+        subprocess.run([EXE, "-f", "-d", snp, dec], check=True, capture_output=True)
+        assert open(dec, "rb").read() == want
+
+
+# ---- errors -------------------------------------------------------------------
+def _errors():
+    p = pieces([3000, 500, 2000], "R")
+    # chunk 0's payload written by hand as one literal, so the byte to change is known to be literal data
+    lit = fm.varint(3000) + bytes([61 << 2, 2999 & 0xFF, 2999 >> 8]) + p[0]
+    c0, s1, c2 = fm.compressed(p[0], lit), fm.stored(p[1]), comp(p[2])
+    good = fm.IDENTIFIER + c0 + s1 + c2
+    at1 = 10 + len(c0)          # the stored chunk's header
+    at2 = at1 + len(s1)         # the last chunk's header
+
+    def flip(b, i, bit=1):
+        b = bytearray(b)
+        b[i] ^= bit
+        return bytes(b)
+
+    # second chunk: literal "abcd", then a 4-byte copy from offset 5 -- one byte
+    # before the chunk's start, a byte that exists in the output (chunk 0's last)
+    back = fm.compressed(b"abcdabcd", fm.varint(8) + bytes([3 << 2]) + b"abcd" + bytes([0x01, 5]))
+    return {
+        "bit flipped in a stored CRC": (flip(good, 10 + 4), snappy_amd.ERR_CHECKSUM),
+        "bit flipped in the last chunk's CRC": (flip(good, at2 + 7, 0x80), snappy_amd.ERR_CHECKSUM),
+        "bit flipped in a stored chunk's data": (flip(good, at1 + 8 + 100), snappy_amd.ERR_CHECKSUM),
+        "literal byte changed in a compressed chunk": (flip(good, 10 + 8 + 1500, 0xFF), snappy_amd.ERR_CHECKSUM),
+        "no identifier": (good[10:], snappy_amd.ERR_HEADER),
+        "identifier with a wrong byte": (flip(good, 7), snappy_amd.ERR_HEADER),
+        "type 02": (good + fm.chunk(0x02, b"abcdef"), snappy_amd.ERR_UNSUPPORTED),
+        "chunk one byte past the end": (good[:-1], snappy_amd.ERR_TRUNCATED),
+        "chunk 2^24 - 1 past the end": (good + b"\x00\xff\xff\xff", snappy_amd.ERR_TRUNCATED),
+        "cut inside a chunk header": (good[:at2 + 3], snappy_amd.ERR_TRUNCATED),
+        "len = 3": (good + b"\x00\x03\x00\x00abc", snappy_amd.ERR_HEADER),
+        "compressed chunk that declares 65,537": (good + fm.chunk(0x00, bytes(4) + fm.varint(65537) + b"\x00a"),
+                                                  snappy_amd.ERR_OVERRUN),
+        "stored chunk of 65,537": (good + fm.stored(bytes(65537)), snappy_amd.ERR_OVERRUN),
+        "copy from one byte before its chunk": (fm.IDENTIFIER + c0 + back, snappy_amd.ERR_OFFSET),
+        "element past an empty chunk's preamble": (good + fm.compressed(b"", fm.varint(0) + b"\x00a"),
+                                                   snappy_amd.ERR_OVERRUN),
+    }, good, b"".join(p)
+
+
+ERRORS, GOOD, GOOD_RAW = _errors()
+
+
+def _decode_with_sentinel(codec, stream, cap):
+    """index + decode through the device API into cap bytes followed by a
+    sentinel; returns (status, output bytes), the sentinel checked."""
+    frame = dev(stream)
+    out = torch.full((cap + 256,), SENT, dtype=torch.uint8, device="cuda")
+    try:
+        n, chunks = codec.frame_index_tensor(frame)
+        got = codec.decompress_frame_tensor(frame, chunks, cap, out=out)
+        rc, res = 0, host(got)
+    except snappy_amd.SnappyError as e:
+        rc, res = e.code, b""
+    assert host(out[cap:]) == bytes([SENT]) * 256, "bytes past cap were written"
+    return rc, res
+
+
+@pytest.mark.parametrize("name", list(ERRORS))
+def test_error_table(codec, name):
+    stream, want = ERRORS[name]
+    rc, _ = _decode_with_sentinel(codec, stream, len(GOOD_RAW) + 16)
+    assert rc == want
+    with pytest.raises(snappy_amd.SnappyError) as e:
+        snappy_amd.decompress_frame(stream, cap=len(GOOD_RAW) + 16)
+    assert e.value.code == want
+    # the context (and the pooled host context) go on working
+    assert _decode_with_sentinel(codec, GOOD, len(GOOD_RAW)) == (0, GOOD_RAW)
+    assert snappy_amd.decompress_frame(GOOD) == GOOD_RAW
+
+
+def test_error_capacity_one_byte_short(codec):
+    rc, _ = _decode_with_sentinel(codec, GOOD, len(GOOD_RAW) - 1)
+    assert rc == snappy_amd.ERR_CAPACITY
+    with pytest.raises(snappy_amd.SnappyError) as e:
+        snappy_amd.decompress_frame(GOOD, cap=len(GOOD_RAW) - 1)
+    assert e.value.code == snappy_amd.ERR_CAPACITY
+    assert _decode_with_sentinel(codec, GOOD, len(GOOD_RAW)) == (0, GOOD_RAW)
+
+
+def test_error_first_failing_chunk_wins(codec):
+    # chunk 1's CRC is wrong and chunk 2 is malformed for the decoder: chunk 1 is reported
+    p = pieces([200, 200, 200], "R")
+    bad_crc = fm.compressed(p[1], oracle.compress(p[1]), crc=0x12345678)
+    bad_elem = fm.compressed(p[2], fm.varint(200) + bytes([60 << 2, 199]))  # a literal with no bytes behind it
+    rc, _ = _decode_with_sentinel(codec, fm.IDENTIFIER + comp(p[0]) + bad_crc + bad_elem, 600)
+    assert rc == snappy_amd.ERR_CHECKSUM
+    rc, _ = _decode_with_sentinel(codec, fm.IDENTIFIER + comp(p[0]) + bad_elem + bad_crc, 600)
+    assert rc == snappy_amd.ERR_TRUNCATED
+
+
+def test_chunk_table_entry_that_is_no_data_chunk(codec):
+    frame = dev(GOOD)
+    chunks = torch.tensor([0, len(GOOD)], dtype=torch.int64, device="cuda")  # entry 0 = the identifier
+    with pytest.raises(snappy_amd.SnappyError) as e:
+        codec.decompress_frame_tensor(frame, chunks, len(GOOD_RAW))
+    assert e.value.code == snappy_amd.ERR_INDEX
+
+
+def test_device_bytes_and_trim_cover_frame_scratch(codec):
+    codec.trim()
+    base = codec.device_bytes()
+    assert _decode_with_sentinel(codec, GOOD, len(GOOD_RAW)) == (0, GOOD_RAW)
+    assert codec.device_bytes() > base
+    codec.trim()
+    assert codec.device_bytes() == base
