@@ -65,8 +65,16 @@ SNAPPY_PRIVATE int ctx_stream(snappy_amd_ctx *c);
 // its own stream.  host_ctx_return gives it back to the pool.
 extern "C" SNAPPY_PRIVATE int host_ctx_lease(void **token, snappy_amd_ctx **ctx);
 extern "C" SNAPPY_PRIVATE void host_ctx_return(void *token);
-// K1r (or K1r64) -> K3 -> K2 on c->stream; *out_len (when non-null) after a
-// sync of that stream, otherwise the size stays in c->total (device)
+// The compress launches of every device compress call, on c->stream, for n > 0
+// bytes in units of `unit` (<= SNAPPY_AMD_BLOCK): the scratch sizing, K1r (or
+// K1r64) with the timing events, after_match(c, units) when given (the framed
+// call adds its chunk headers to c->sizes there), K3 into d_offsets (units + 1
+// entries, the total in c->total) and K2 to d_out.  hdr_mode: SNAPPY_HDR_*.
+SNAPPY_PRIVATE int compress_launch(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit, uint32_t hdr_mode,
+                                   uint64_t header_value, uint64_t *d_offsets, void *d_out,
+                                   void (*after_match)(snappy_amd_ctx *c, size_t units));
+// the argument checks, the n == 0 case and compress_launch for a layout; *out_len
+// (when non-null) after a sync of c->stream, otherwise the size stays in c->total (device)
 extern "C" SNAPPY_PRIVATE int compress_impl(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk, int layout,
                                  uint32_t flags, uint64_t header_value, void *d_out, uint64_t *d_offsets,
                                  size_t *out_len);

@@ -45,6 +45,59 @@ int ctx_stream(snappy_amd_ctx *c)
     return SNAPPY_AMD_OK;
 }
 
+// register-resident match finder -> tokens; scan; emit in place
+int compress_launch(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit, uint32_t hm, uint64_t header_value,
+                    uint64_t *d_offsets, void *d_out, void (*after_match)(snappy_amd_ctx *c, size_t units))
+{
+    const size_t units = (n + unit - 1) / unit;
+    int rc;
+    const uint32_t tok_cap = unit / 4 + 2;
+    if ((rc = grow(reinterpret_cast<void **>(&c->tokens), &c->tokens_cap,
+                   units * tok_cap * sizeof(uint2) + units * 4 * sizeof(uint64_t))))
+        return rc;
+    if ((rc = grow(reinterpret_cast<void **>(&c->ntok), &c->ntok_cap, units * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(reinterpret_cast<void **>(&c->sizes), &c->sizes_cap, units * sizeof(uint32_t)))) return rc;
+    // segments per unit: tokens 0..ntok (the tail literal is token ntok <= tok_cap - 1)
+    const uint32_t segs = (tok_cap + SNAPPY_K2_SEG - 1) / SNAPPY_K2_SEG;
+    if ((rc = grow(reinterpret_cast<void **>(&c->seg_off), &c->seg_off_cap, units * segs * 2 * sizeof(uint32_t))))
+        return rc;
+    // launch errors are read with hipGetLastError: clear one a runtime call of
+    // the caller's (or of another context on this thread) left pending
+    (void)hipGetLastError();
+    if (c->timing) (void)hipEventRecord(c->ev[0], c->stream);
+    // units <= 32 KiB: the unit in 128 VGPRs; 65,536-byte blocks: its last 128
+    // segments in a 128-VGPR ring fed by LDS-DMA (both 3 waves/SIMD, DESIGN.md 3).
+    // Extra dynamic LDS per unit: occupancy experiments only (SNAPPY_AMD_OPT_K1R_EXTRA_LDS)
+    const uint32_t dyn_lds = c->k1r_extra_lds;
+    if (unit <= SNAPPY_K1R_MAX_UNIT)
+        hipLaunchKernelGGL(k1r_match_units, dim3((uint32_t)units), dim3(64), dyn_lds, c->stream,
+                           static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
+                           static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
+    else
+        hipLaunchKernelGGL(k1r_match_units64, dim3((uint32_t)units), dim3(64), 0, c->stream,
+                           static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
+                           static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
+    HIP_OK(hipGetLastError());
+    if (c->timing) (void)hipEventRecord(c->ev[1], c->stream);
+    if (after_match) after_match(c, units);
+    if (units <= SNAPPY_K3_WAVE_MAX)
+        hipLaunchKernelGGL(k3_scan_wave, dim3(1), dim3(64), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
+    else
+        hipLaunchKernelGGL(k3_scan, dim3(1), dim3(1024), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
+    // K1r wrote the sizes and segment offsets; K2: a few waves per unit, each taking
+    // every SNAPPY_K2_WAVES-th segment (text fills ~12 segments of 32 KiB units)
+    hipLaunchKernelGGL(k2_emit_units, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES), dim3(64), 0, c->stream,
+                       static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
+                       static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs, d_offsets,
+                       static_cast<uint8_t *>(d_out));
+    HIP_OK(hipGetLastError());
+    if (c->timing) {
+        (void)hipEventRecord(c->ev[2], c->stream);
+        c->ev_compress = true;
+    }
+    return SNAPPY_AMD_OK;
+}
+
 extern "C" {
 
 const char *snappy_amd_config_compress(void);
@@ -220,56 +273,8 @@ int compress_impl(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk,
         if (out_len) *out_len = 0;
         return SNAPPY_AMD_OK;
     }
-    const size_t units = (n + unit - 1) / unit;
-    int rc;
-    // (snappy_amd_compress_frame_device, snappy_frame.hip, repeats the scratch sizing and the
-    // K1r64 / K3 / K2 launches below for units of 65,536 with a kernel of its own between
-    // K1r64 and K3: a change to either here has to be made there too)
-    // register-resident match finder -> tokens; scan; emit in place
-    const uint32_t tok_cap = unit / 4 + 2;
-    if ((rc = grow(reinterpret_cast<void **>(&c->tokens), &c->tokens_cap,
-                   units * tok_cap * sizeof(uint2) + units * 4 * sizeof(uint64_t))))
-        return rc;
-    if ((rc = grow(reinterpret_cast<void **>(&c->ntok), &c->ntok_cap, units * sizeof(uint32_t)))) return rc;
-    if ((rc = grow(reinterpret_cast<void **>(&c->sizes), &c->sizes_cap, units * sizeof(uint32_t)))) return rc;
-    // segments per unit: tokens 0..ntok (the tail literal is token ntok <= tok_cap - 1)
-    const uint32_t segs = (tok_cap + SNAPPY_K2_SEG - 1) / SNAPPY_K2_SEG;
-    if ((rc = grow(reinterpret_cast<void **>(&c->seg_off), &c->seg_off_cap, units * segs * 2 * sizeof(uint32_t))))
-        return rc;
-    const uint32_t hm = hdr_mode_of(layout, flags);
-    // launch errors are read with hipGetLastError: clear one a runtime call of
-    // the caller's (or of another context on this thread) left pending
-    (void)hipGetLastError();
-    if (c->timing) (void)hipEventRecord(c->ev[0], c->stream);
-    // units <= 32 KiB: the unit in 128 VGPRs; 65,536-byte blocks: its last 128
-    // segments in a 128-VGPR ring fed by LDS-DMA (both 3 waves/SIMD, DESIGN.md 3).
-    // Extra dynamic LDS per unit: occupancy experiments only (SNAPPY_AMD_OPT_K1R_EXTRA_LDS)
-    const uint32_t dyn_lds = c->k1r_extra_lds;
-    if (unit <= SNAPPY_K1R_MAX_UNIT)
-        hipLaunchKernelGGL(k1r_match_units, dim3((uint32_t)units), dim3(64), dyn_lds, c->stream,
-                           static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
-                           static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
-    else
-        hipLaunchKernelGGL(k1r_match_units64, dim3((uint32_t)units), dim3(64), 0, c->stream,
-                           static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
-                           static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
-    HIP_OK(hipGetLastError());
-    if (c->timing) (void)hipEventRecord(c->ev[1], c->stream);
-    if (units <= SNAPPY_K3_WAVE_MAX)
-        hipLaunchKernelGGL(k3_scan_wave, dim3(1), dim3(64), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
-    else
-        hipLaunchKernelGGL(k3_scan, dim3(1), dim3(1024), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
-    // K1r wrote the sizes and segment offsets; K2: a few waves per unit, each taking
-    // every SNAPPY_K2_WAVES-th segment (text fills ~12 segments of 32 KiB units)
-    hipLaunchKernelGGL(k2_emit_units, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES), dim3(64), 0, c->stream,
-                       static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
-                       static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs, d_offsets,
-                       static_cast<uint8_t *>(d_out));
-    HIP_OK(hipGetLastError());
-    if (c->timing) {
-        (void)hipEventRecord(c->ev[2], c->stream);
-        c->ev_compress = true;
-    }
+    int rc = compress_launch(c, d_in, n, unit, hdr_mode_of(layout, flags), header_value, d_offsets, d_out, nullptr);
+    if (rc) return rc;
     if (out_len) {
         HIP_OK(hipMemcpyAsync(c->h_total, c->total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
@@ -317,7 +322,7 @@ static int decompress_launch(snappy_amd_ctx *c, const void *d_comp, const uint64
     // reach into earlier blocks (src/snappy_decompression.c:253-280, 345-363);
     // pass 1 decodes every self-contained block, pass 2 the others in order
     const uint32_t allow_back = layout == SNAPPY_AMD_SINGLE ? 1u : 0u;
-    (void)hipGetLastError();  // (a pending error that is not this launch's, as in compress_impl)
+    (void)hipGetLastError();  // (a pending error that is not this launch's, as in compress_launch)
     if (c->timing) (void)hipEventRecord(c->ev[3], c->stream);
     if (allow_back) HIP_OK(hipMemsetAsync(c->status + units, 0, 2 * sizeof(int32_t), c->stream));
     const uint32_t hm = hdr_mode_of(layout, flags);
@@ -402,7 +407,7 @@ int snappy_amd_index_device(snappy_amd_ctx *c, const void *d_comp, size_t clen, 
     if (!c || !d_comp || !d_offsets) return SNAPPY_AMD_ERR_ARG;
     HIP_OK(hipSetDevice(c->device));
     if (ctx_stream(c)) return SNAPPY_AMD_ERR_DEVICE;
-    (void)hipGetLastError();  // (a pending error that is not this launch's, as in compress_impl)
+    (void)hipGetLastError();  // (a pending error that is not this launch's, as in compress_launch)
     const uint8_t *comp = static_cast<const uint8_t *>(d_comp);
     const bool serial = c->serial_index;
     if (!serial && clen >= 4 * (size_t)K5_CHUNK && (reinterpret_cast<uintptr_t>(d_comp) & 3)) {

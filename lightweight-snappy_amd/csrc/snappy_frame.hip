@@ -11,8 +11,9 @@
 //        kf4_verify      stored CRC against KF1's over the decoded bytes
 //
 // The match finder, the scan, the emitter (K1r64, K3, K2) and the decoder (K4)
-// are the unframed path's kernels, launched from here unchanged: a framed
-// chunk's payload is exactly a STREAMS unit of 65,536 bytes.  Declared in
+// are the unframed path's kernels, unchanged (the compress ones through the
+// unframed path's own compress_launch, snappy_device.hip): a framed chunk's
+// payload is exactly a STREAMS unit of 65,536 bytes.  Declared in
 // include/snappy_amd.h.  DESIGN.md 7.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -383,7 +384,7 @@ int frame_call_begin(snappy_amd_ctx *c)
 {
     HIP_OK(hipSetDevice(c->device));
     if (ctx_stream(c)) return SNAPPY_AMD_ERR_DEVICE;
-    (void)hipGetLastError();  // (a pending error that is not this call's, as in compress_impl)
+    (void)hipGetLastError();  // (a pending error that is not this call's, as in compress_launch)
     return SNAPPY_AMD_OK;
 }
 
@@ -430,36 +431,17 @@ int snappy_amd_compress_frame_device(snappy_amd_ctx *c, const void *d_in, size_t
     uint64_t *f_off = nullptr;
     uint32_t *f_crc = nullptr;
     if (units) {
-        // K1r64 -> (+8) -> K3 -> K2 as compress_impl launches them for STREAMS units of 65,536
-        const uint32_t tok_cap = unit / 4 + 2;
-        if ((rc = grow(reinterpret_cast<void **>(&c->tokens), &c->tokens_cap,
-                       units * tok_cap * sizeof(uint2) + units * 4 * sizeof(uint64_t))))
-            return rc;
-        if ((rc = grow(reinterpret_cast<void **>(&c->ntok), &c->ntok_cap, units * sizeof(uint32_t)))) return rc;
-        if ((rc = grow(reinterpret_cast<void **>(&c->sizes), &c->sizes_cap, units * sizeof(uint32_t)))) return rc;
-        const uint32_t segs = (tok_cap + SNAPPY_K2_SEG - 1) / SNAPPY_K2_SEG;
-        if ((rc = grow(reinterpret_cast<void **>(&c->seg_off), &c->seg_off_cap, units * segs * 2 * sizeof(uint32_t))))
-            return rc;
         if ((rc = grow(reinterpret_cast<void **>(&c->f_meta), &c->f_meta_cap,
                        (units + 1) * sizeof(uint64_t) + units * sizeof(uint32_t))))
             return rc;
         f_off = reinterpret_cast<uint64_t *>(c->f_meta);
         f_crc = reinterpret_cast<uint32_t *>(f_off + units + 1);
-        const uint32_t hm = SNAPPY_HDR_EVERY_UNIT;
-        hipLaunchKernelGGL(k1r_match_units64, dim3((uint32_t)units), dim3(64), 0, c->stream,
-                           static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, (uint64_t)n,
-                           static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(kf2_bump, dim3(blocks_of(units, 256)), dim3(256), 0, c->stream, c->sizes, (uint64_t)units);
-        if (units <= SNAPPY_K3_WAVE_MAX)
-            hipLaunchKernelGGL(k3_scan_wave, dim3(1), dim3(64), 0, c->stream, c->sizes, (uint64_t)units, f_off, c->total);
-        else
-            hipLaunchKernelGGL(k3_scan, dim3(1), dim3(1024), 0, c->stream, c->sizes, (uint64_t)units, f_off, c->total);
-        hipLaunchKernelGGL(k2_emit_units, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES),
-                           dim3(64), 0, c->stream, static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm,
-                           (uint64_t)n, static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs,
-                           f_off, out + ident + 8);
-        HIP_OK(hipGetLastError());
+        // STREAMS units of 65,536, with kf2_bump between K1r64 and the scan (KF2 above)
+        auto bump = [](snappy_amd_ctx *cc, size_t nu) {
+            hipLaunchKernelGGL(kf2_bump, dim3(blocks_of(nu, 256)), dim3(256), 0, cc->stream, cc->sizes, (uint64_t)nu);
+        };
+        if ((rc = compress_launch(c, d_in, n, unit, SNAPPY_HDR_EVERY_UNIT, (uint64_t)n, f_off, out + ident + 8, bump)))
+            return rc;
         launch_kf1(c, d_in, nullptr, units, unit, n, 1, f_crc);
     }
     hipLaunchKernelGGL(kf2_headers, dim3(units ? blocks_of(units, 256) : 1u), dim3(256), 0, c->stream, out, ident,

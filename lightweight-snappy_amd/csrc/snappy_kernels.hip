@@ -126,31 +126,14 @@ constexpr uint32_t kRegs = 128;  // VGPRs holding a 32 KiB unit (64 dwords each)
 // take as an asm clobber.  The statements leave m0 holding the index: the
 // built code object is checked to set m0 again before any later read of it
 // (tools/check_asm_waits.py check_m0, run by tests/test_abi.py).
-// SNAPPY_REGIDX_M0_SAVE 1 saves and restores m0 inside each statement instead
-// (A/B, outputs identical: K1r +1.1 %, K1r64 +0.5 %, profiles/r06w_*).
-#ifndef SNAPPY_REGIDX_M0_SAVE
-#define SNAPPY_REGIDX_M0_SAVE 0
-#endif
-#if SNAPPY_REGIDX_M0_SAVE
-#define REGIDX_M0_DECL uint32_t _m0;
-#define REGIDX_M0_SAVE "s_mov_b32 %[m0s], m0\n\t"
-#define REGIDX_M0_REST "\n\ts_mov_b32 m0, %[m0s]"
-#define REGIDX_M0_OUT , [m0s] "=&s"(_m0)
-#define REGIDX_M0_ONLY [m0s] "=&s"(_m0)
-#else
-#define REGIDX_M0_DECL
-#define REGIDX_M0_SAVE ""
-#define REGIDX_M0_REST ""
-#define REGIDX_M0_OUT
-#define REGIDX_M0_ONLY
-#endif
+// Saving and restoring m0 inside each statement instead measured slower (A/B,
+// outputs identical: K1r +1.1 %, K1r64 +0.5 %, profiles/r06w_*).
 #define REG_OF_V(r)                                                                                 \
     ({                                                                                              \
         uint32_t _v;                                                                                \
-        REGIDX_M0_DECL                                                                              \
-        asm volatile(REGIDX_M0_SAVE "s_set_gpr_idx_on %[ri], gpr_idx(SRC0)\n\tv_mov_b32 %[ov], v2\n\t"     \
-                     "s_set_gpr_idx_off" REGIDX_M0_REST                                            \
-                     : [ov] "=&v"(_v) REGIDX_M0_OUT                                                  \
+        asm volatile("s_set_gpr_idx_on %[ri], gpr_idx(SRC0)\n\tv_mov_b32 %[ov], v2\n\t"             \
+                     "s_set_gpr_idx_off"                                                            \
+                     : [ov] "=&v"(_v)                                                               \
                      : [ri] "s"((uint32_t)(r)), "{v[2:33]}"(g0), "{v[34:65]}"(g1), "{v[66:97]}"(g2),      \
                        "{v[98:129]}"(g3));                                                          \
         _v;                                                                                         \
@@ -165,10 +148,9 @@ constexpr uint32_t kRegs = 128;  // VGPRs holding a 32 KiB unit (64 dwords each)
 // place with no VGPR spills (tests/test_abi.py::test_kernel_register_budget).
 #define REG_SET_V(r, val)                                                                            \
     do {                                                                                             \
-        REGIDX_M0_DECL                                                                               \
-        asm volatile(REGIDX_M0_SAVE "s_set_gpr_idx_on %[ri], gpr_idx(DST)\n\tv_mov_b32 v2, %[xv]\n\t"       \
-                     "s_set_gpr_idx_off" REGIDX_M0_REST                                             \
-                     : REGIDX_M0_ONLY                                                                \
+        asm volatile("s_set_gpr_idx_on %[ri], gpr_idx(DST)\n\tv_mov_b32 v2, %[xv]\n\t"               \
+                     "s_set_gpr_idx_off"                                                             \
+                     :                                                                               \
                      : [ri] "s"((uint32_t)(r)), [xv] "v"(val), "{v[2:33]}"(g0), "{v[34:65]}"(g1),        \
                        "{v[66:97]}"(g2), "{v[98:129]}"(g3) : "memory");                              \
     } while (0)
@@ -186,10 +168,9 @@ constexpr uint32_t kRegs = 128;  // VGPRs holding a 32 KiB unit (64 dwords each)
 // which holds no unit data (see DW_LANES)
 #define REG_PAIR_V(r, lo, hi)                                                                        \
     do {                                                                                             \
-        REGIDX_M0_DECL                                                                               \
-        asm volatile(REGIDX_M0_SAVE "s_set_gpr_idx_on %[ri], gpr_idx(SRC0)\n\tv_mov_b32 %[olo], v2\n\t"      \
-                     "v_mov_b32 %[ohi], v3\n\ts_set_gpr_idx_off" REGIDX_M0_REST                        \
-                     : [olo] "=&v"(lo), [ohi] "=&v"(hi) REGIDX_M0_OUT                                  \
+        asm volatile("s_set_gpr_idx_on %[ri], gpr_idx(SRC0)\n\tv_mov_b32 %[olo], v2\n\t"             \
+                     "v_mov_b32 %[ohi], v3\n\ts_set_gpr_idx_off"                                     \
+                     : [olo] "=&v"(lo), [ohi] "=&v"(hi)                                              \
                      : [ri] "s"((uint32_t)(r)), "{v[2:33]}"(g0), "{v[34:65]}"(g1), "{v[66:97]}"(g2),      \
                        "{v[98:129]}"(g3));                                                           \
     } while (0)
@@ -662,15 +643,12 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     uint32_t pdnz = 0;  // the predecessor's tag
     uint64_t m_win = 0, m_win17 = 0;
     bool lsw = false;  // the lane-space data describe the current window
-// SNAPPY_K1R_WIN_ALIGN: a window's per-lane BE32 by v_alignbit from (p - 1) / 4
-// (as the round loop's pa funnel, V6) instead of v_perm with a per-lane
-// selector from a 32-bit multiply; 32 KiB units only (A/B, outputs identical,
-// profiles/r05zj_*: 32 KiB streams 12.64 -> 12.55-12.57 ms per GiB, but 64 KiB
-// blocks 14.06 -> 14.41 in K1r64's schedule)
-#ifndef SNAPPY_K1R_WIN_ALIGN
-#define SNAPPY_K1R_WIN_ALIGN 1
-#endif
-#define WINDOW_AT(qq)                                                                              \
+// 32 KiB units take a window's per-lane BE32 by v_alignbit from (p - 1) / 4
+// (as the round loop's pa funnel, V6); K1r64 keeps v_perm with a per-lane
+// selector from a 32-bit multiply (A/B, outputs identical, profiles/r05zj_*:
+// 32 KiB streams 12.64 -> 12.55-12.57 ms per GiB, but 64 KiB blocks
+// 14.06 -> 14.41 in K1r64's schedule)
+#define WINDOW_AT(qq)                                                                             \
     do {                                                                                           \
         q0 = (qq);                                                                                 \
         ring_to((q0 >> 8) + 2, std::true_type{}); /* BIG: the window's segments and the next */    \
@@ -681,7 +659,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             REG_PAIR(d0 >> 6, _r0, _r1);                                                           \
             dv = lane >= dr ? _r0 : _r1;                                                           \
         }                                                                                          \
-        if (SNAPPY_K1R_WIN_ALIGN == 2 || (SNAPPY_K1R_WIN_ALIGN && !BIG)) { \
+        if (!BIG) {                                                                                \
             /* the dwords from (p - 1) / 4 funnelled by v_alignbit with the lane's */              \
             /* shift -8 p (bits 4:0; 0 takes the second dword, the one at p) */                    \
             const uint32_t _p = q0 + lane;                                                          \
@@ -878,22 +856,19 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // left to the code around the statement.  The padding (s_nop) runs once per
 // entry into the asm loop.  Re-swept with DMAX 13 / 12 and RMIN 2 (profiles/
 // r06n_*): PAD32 0..15 -> 12.18 (2) to 12.79 (13) ms per GiB; PAD64 -1 13.93,
-// 0..14 even 14.00-14.55.  With SNAPPY_K1R_X45 (r06x_*): PAD32 0 best (12.13-12.20;
-// 12.20-12.53 elsewhere), PAD64 -1 best (13.85-13.88; 13.92-14.53 pinned).
+// 0..14 even 14.00-14.55.  With the one length test of the hit round (r06x_*): PAD32 0
+// best (12.13-12.20; 12.20-12.53 elsewhere), PAD64 -1 best (13.85-13.88; 13.92-14.53 pinned).
 // With the window refresh inside K1r's statement (profiles/r08b_*): PAD32 0..15 ->
 // 11.12-11.14 (2 and 10) to 11.46-11.49 (15) ms per GiB, the parent 11.91-11.92.
 #ifndef SNAPPY_K1R_PAD32
-#define SNAPPY_K1R_PAD32 2  // with SNAPPY_K1R_WIN_INLOOP (profiles/r08b_*), and again with the flush and the
-                            // tag-collision round inside the statement (r09b_*: 2 and 10 best of 0..15)
+#define SNAPPY_K1R_PAD32 2  // with the window refresh inside the statement (profiles/r08b_*), and again with the
+                            // flush and the tag-collision round inside it (r09b_*: 2 and 10 best of 0..15)
 #endif
 #ifndef SNAPPY_K1R_PAD64
-#define SNAPPY_K1R_PAD64 0  // with SNAPPY_K1R64_HALF32 (profiles/r06aa_*, r06ad_*)
+#define SNAPPY_K1R_PAD64 0  // with K1r64's first-32-KiB loop, K1R64_HALF_LOOP (profiles/r06aa_*, r06ad_*)
 #endif
-#ifndef SNAPPY_K1R_PAD64A  // K1r64's first-32-KiB loop (SNAPPY_K1R64_HALF32; -1 with EARLY_DK, r06ah_*)
+#ifndef SNAPPY_K1R_PAD64A  // K1r64's first-32-KiB loop (-1 with the early token offset, r06ah_*)
 #define SNAPPY_K1R_PAD64A -1
-#endif
-#ifndef SNAPPY_K1R64_HALF32
-#define SNAPPY_K1R64_HALF32 1
 #endif
 #define K1R_STR2(x) #x
 #define K1R_STR(x) K1R_STR2(x)
@@ -914,9 +889,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "src0_sel:DWORD src1_sel:WORD_0\n\t" /* the candidate of every lane */                          \
     "v_cndmask_b32_e32 %[t0], %[pdnz], %[entt], vcc\n\t" /* and its tag */                          \
     "v_cmp_eq_u32_sdwa %[hm], %[t0], %[word] src0_sel:DWORD src1_sel:WORD_1\n\t"
-#define K1R_HIT32 K1R_HIT_PREDTAG
-#define K1R_HIT64 K1R_HIT_PREDTAG
-#define K1R_DRAIN                                                                                   \
+#define K1R_DRAIN                                                                                  \
     "s_mov_b32 m0, %[pend]\n\t" /* (gfx950 refuses two SGPRs in a v_writelane: m0 stays) */          \
     "v_writelane_b32 %[tka], %[dka], m0\n\t"                                                        \
     "v_writelane_b32 %[tkb], %[dkb], m0\n\t"                                                        \
@@ -931,32 +904,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_mov_b64 exec, %[sx]\n\t"                                                                     \
     "ds_read_u16 %[ent], %[adr]\n\t" /* the next round's entries */                                  \
     "ds_read_u8 %[entt], %[adrt] offset:%[tagb]\n\t"
-// the match length: lane s1 (the first differing dword of the 64 bytes, -1 if
-// none in lanes 0-31) gives 4 s1 + the byte.  SNAPPY_K1R_X45: one unsigned test
-// of len - 4 > 59 leaves for both rare ends (>= 64 equal bytes: s1 > 15, or -1,
-// whose lane 63 reads >= 252; a tag collision: len < 4), told apart at the exit:
-// one compare and one branch fewer per hit round, K1r 12.18-12.24 -> 12.11-12.17 ms
-// per GiB and K1r64 13.94-13.98 -> 13.82-13.86, each at its best loop placement
-// (profiles/r06x_*, r06y_*, outputs identical)
-#ifndef SNAPPY_K1R_X45
-#define SNAPPY_K1R_X45 1
-#endif
-#if SNAPPY_K1R_X45
-#define K1R_LENCHECK                                                                                \
-    "v_readlane_b32 %[s0], %[t2], %[s1]\n\t"                                                        \
-    "s_add_u32 %[s2], %[s0], -4\n\t"                                                                \
-    "s_cmp_gt_u32 %[s2], 59\n\t"                                                                    \
-    "s_cbranch_scc1 L%=_x4\n\t"
-#define K1R_X4 "s_cmp_lt_u32 %[s0], 4\n\ts_cbranch_scc1 L%=_x5\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n"
-#else
-#define K1R_LENCHECK                                                                                \
-    "s_cmp_gt_u32 %[s1], 15\n\t"                                                                    \
-    "s_cbranch_scc1 L%=_x4\n\t"                                                                    \
-    "v_readlane_b32 %[s0], %[t2], %[s1]\n\t"                                                       \
-    "s_cmp_lt_u32 %[s0], 4\n\t" /* (pf <= L - 16: the clamp below never makes it < 4) */           \
-    "s_cbranch_scc1 L%=_x5\n\t"
-#define K1R_X4 "s_mov_b32 %[code], 4\n\ts_branch L%=_end\n"
-#endif
 // the miss round's way on: the four tests in turn
 #define K1R_NOHIT_TAIL(T)                                                                           \
     "s_cmp_gt_u32 %[skip], %[lsmax]\n\t"                                                           \
@@ -967,30 +914,27 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_cbranch_scc1 L%=_win\n\t"                                                                    \
     "s_cmp_le_u32 %[skip], %[skipmax]\n\t"                                                         \
     "s_cbranch_scc1 L%=_top" T "\n"
-// SNAPPY_K1R_EARLY_DK: a hit round's token offset written right after the drain
-// that consumed the previous one (in the gather wait's shadow) instead of on the
-// tail after the length read-back.  (The pending flag stays on the tail: the
-// code-5 exit's skip fix reads the previous round's.)  A/B, outputs identical,
+// One round loop of the asm statement (labels suffixed with T).
+// The token offset: a hit round's dkb = pf - c is written right after the drain
+// that consumed the previous one (in the gather wait's shadow), not on the tail
+// after the length read-back.  (The pending flag dkn stays on the tail: the tag
+// collision's skip fix reads the previous round's.)  A/B, outputs identical,
 // 68 GPU tests green, at each build's best placements (profiles/r06ag_*, r06ah_*):
-// K1r 12.11-12.13 -> 12.04-12.08 ms per GiB, K1r64 13.55-13.60 -> 13.49-13.51
-#ifndef SNAPPY_K1R_EARLY_DK
-#define SNAPPY_K1R_EARLY_DK 1
-#endif
-#if SNAPPY_K1R_EARLY_DK
-#define K1R_DK_EARLY "s_sub_u32 %[dkb], %[pf], %[c]\n\t"
-#define K1R_DK_LATE "s_mov_b32 %[dkn], 1\n\t"
-#else
-#define K1R_DK_EARLY
-#define K1R_DK_LATE "s_sub_u32 %[dkb], %[pf], %[c]\n\ts_mov_b32 %[dkn], 1\n\t"
-#endif
-// one round loop of the asm statement (labels suffixed with T)
-#define K1R_ROUND_BODY(CAND, HIT, T)                                                                \
+// K1r 12.11-12.13 -> 12.04-12.08 ms per GiB, K1r64 13.55-13.60 -> 13.49-13.51.
+// The match length: lane s1 (the first differing dword of the 64 bytes, -1 if
+// none in lanes 0-31) gives 4 s1 + the byte.  One unsigned test of len - 4 > 59
+// leaves for both rare ends (>= 64 equal bytes: s1 > 15, or -1, whose lane 63
+// reads >= 252; a tag collision: len < 4), told apart at _x4: one compare and
+// one branch fewer per hit round than a test for each, K1r 12.18-12.24 ->
+// 12.11-12.17 ms per GiB and K1r64 13.94-13.98 -> 13.82-13.86, each at its best
+// loop placement (profiles/r06x_*, r06y_*, outputs identical)
+#define K1R_ROUND_BODY(CAND, T)                                                                     \
             "L%=_top" T ":\n\t"                                                                          \
             "s_lshl_b64 %[valid], %[dmask], %[lane0]\n\t"                                           \
             "v_cmp_gt_i32_e32 vcc, %[lane0], %[pdl1]\n\t" /* vcc = not in-round */                  \
             "s_waitcnt lgkmcnt(0)\n\t"                                                              \
-            HIT                                                                                     \
-            "s_and_b64 %[hm], %[hm], %[valid]\n\t"                                                  \
+            K1R_HIT_PREDTAG                                                                         \
+            "s_and_b64 %[hm], %[hm], %[valid]\n\t"                                                \
             "s_cbranch_scc0 L%=_nohit" T "\n\t" /* SCC = (hm != 0) */                                     \
             "s_ff1_i32_b64 %[f], %[hm]\n\t"                                                         \
             "v_readlane_b32 %[c], %[t1], %[f]\n\t"                                                  \
@@ -1007,7 +951,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "ds_bpermute_b32 %[t3], %[t1], %[t3]\n\t" /* ca: dwords at c */                         \
             "L%=_farret" T ":\n\t"                                                                       \
             K1R_DRAIN /* the previous round's token, during the gathers */                         \
-            K1R_DK_EARLY                                                                            \
+            "s_sub_u32 %[dkb], %[pf], %[c]\n\t" /* this round's token offset */                     \
             "s_cmp_lt_u32 %[lane0], %[f]\n\t"                                                       \
             "s_subb_u32 %[s0], %[lane0], 0\n\t" /* lo0 */                                           \
             "v_mul_i32_i24_e64 %[t0], %[pf], -8\n\t" /* pa's funnel shift */                        \
@@ -1028,10 +972,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "v_bfe_u32 %[t2], %[t2], 3, 2\n\t"                                                      \
             "v_lshl_or_b32 %[t2], %[lane], 2, %[t2]\n\t" /* the prefix length if this dword differs */ \
             "s_ff1_i32_b32 %[s1], vcc_lo\n\t"                                                       \
-            K1R_LENCHECK                                                                            \
+            "v_readlane_b32 %[s0], %[t2], %[s1]\n\t" /* len */                                      \
+            "s_add_u32 %[s2], %[s0], -4\n\t"                                                        \
+            "s_cmp_gt_u32 %[s2], 59\n\t"                                                            \
+            "s_cbranch_scc1 L%=_x4\n\t" /* >= 64 equal bytes, or a tag collision */                 \
             "s_add_u32 %[lane0], %[f], %[s0]\n\t"                                                   \
             "s_pack_ll_b32_b16 %[dka], %[pf], %[s0]\n\t"                                           \
-            K1R_DK_LATE                                                                             \
+            "s_mov_b32 %[dkn], 1\n\t"                                                               \
             "s_cmp_le_i32 %[lane0], %[lim0]\n\t" /* implies pf + len <= L - 16: no clamp */         \
             "s_cbranch_scc1 L%=_top" T "\n\t"                                                            \
             "s_sub_u32 %[s2], %[L], %[pf]\n\t" /* leaving: the length clamped to the block end */ \
@@ -1060,7 +1007,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "s_add_u32 %[p], %[q0], %[lane0]\n\t"                                                   \
             "s_mov_b32 %[skip], %[s2]\n\t"                                                          \
             K1R_NOHIT_TAIL(T)
-// SNAPPY_K1R64_HALF32: K1r64's asm statement holds a second round loop with the
+// K1R64_HALF_LOOP: K1r64's asm statement holds a second round loop with the
 // 32 KiB candidate step, entered while no segment past the first 128 is loaded
 // (seghi == 0: registers 0..127 hold segments 0..127, nothing is far or wrapped;
 // a pair past register 127 reads v130 only for bytes past the 64 the round
@@ -1069,18 +1016,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // outputs identical, 68 GPU tests green: K1r64 13.78-13.82 -> 13.52-13.56 ms per
 // GiB with both loops' placements swept (PAD64 0, PAD64A 0; profiles/r06aa_*,
 // r06ad_*); random and repeat equal
-#if SNAPPY_K1R64_HALF32
 #define K1R64_HALF_SEL "s_cmp_eq_u32 %[seghi], 0\n\ts_cbranch_scc1 L%=_topa\n"
 // (the first loop's miss path falls through to the code-3 exit: branch there)
-#define K1R64_HALF_LOOP "s_branch L%=_x3\n" K1R_LOOP_PLACE(SNAPPY_K1R_PAD64A) K1R_ROUND_BODY(K1R_CAND32, K1R_HIT64, "a")
-#else
-#define K1R64_HALF_SEL ""
-#define K1R64_HALF_LOOP ""
-#endif
-// SNAPPY_K1R_WIN_INLOOP: K1r's window refresh as a path of the statement (_win)
+#define K1R64_HALF_LOOP "s_branch L%=_x3\n" K1R_LOOP_PLACE(SNAPPY_K1R_PAD64A) K1R_ROUND_BODY(K1R_CAND32, "a")
+// K1R_WIN_PATH: K1r's window refresh as a path of the statement (_win)
 // instead of a code-2 exit, the C++ WINDOW_LS and a re-entry, when no token
 // flush is due (pend + dkn <= 48: 444 of a 32 KiB text unit's 518 refreshes).
-// It is WINDOW_LS(p - 1) for !BIG with SNAPPY_K1R_WIN_ALIGN, instruction for
+// It is WINDOW_LS(p - 1) for !BIG (the v_alignbit form), instruction for
 // instruction the compiler's own schedule of it: the register pair of q0 / 256
 // under s_set_gpr_idx_on, two ds_bpermute and v_alignbit for each lane's BE32,
 // the kMul hash with its tag, the new entries read as soon as their addresses
@@ -1100,12 +1042,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // instruction).  A/B on 1 GiB of 32 KiB text streams, outputs identical, at all
 // 16 loop placements (profiles/r08b_*): 11.91-11.93 ms -> 11.13 at the pinned
 // placement; a unit enters the statement 111 times instead of 549 (r08a_*).
-// SNAPPY_K1R_WIN_INLOOP 0 is the parent's flow (every refresh by exit), kept for
-// the stamped measurement of that flow's glue and as the A/B control.
-#ifndef SNAPPY_K1R_WIN_INLOOP
-#define SNAPPY_K1R_WIN_INLOOP 1
-#endif
-// SNAPPY_K1R_FLUSH_INLOOP: the token flush of a refresh (pend + dkn > 48: 74 of a
+// K1R_FLUSH_PATH: the token flush of a refresh (pend + dkn > 48: 74 of a
 // 32 KiB text unit's refreshes) as a path of K1r's statement instead of a code-2
 // exit, the C++ flush_tokens() and WINDOW_LS and a re-entry.  _fl does what
 // flush_tokens() does for tokens of the short form and goes on into the refresh
@@ -1130,12 +1067,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // A/B on 1 GiB of 32 KiB text streams, outputs identical (profiles/r09b_*): the
 // parent 11.12-11.13 ms, with this path 10.98-10.99, with K1R_X5_PATH as well
 // 10.91-10.94; a unit enters the statement 10.5 times instead of 111 (r09a_*).
-// SNAPPY_K1R_FLUSH_INLOOP 0 is the parent's flow and operand list.
-#ifndef SNAPPY_K1R_FLUSH_INLOOP
-#define SNAPPY_K1R_FLUSH_INLOOP 1
-#endif
-#if SNAPPY_K1R_FLUSH_INLOOP
-#define K1R_FLUSH_TARGET "_fl"
 #define K1R_FLUSH_SCAN(ctrl) "v_add_u32_dpp %[pdc], %[pdc], %[pdc] " ctrl " bank_mask:0xf bound_ctrl:1\n\t"
 #define K1R_FLUSH_PATH                                                                              \
     "L%=_fl:\n\t"                                                                                   \
@@ -1217,26 +1148,15 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_add_u32 %[nt], %[nt], %[pend]\n\t"                                                           \
     "s_mov_b32 %[pend], 0\n\t"                                                                      \
     "s_branch L%=_wr\n"
-#define K1R_FLUSHOPS_OUT , [nt] "+s"(nt), [acc] "+s"(acc), [cend] "+s"(cend)
-#define K1R_FLUSHOPS_IN [tokb] "s"(tok), [segb] "s"(segu),
-#else
-#define K1R_FLUSH_TARGET "_x2"
-#define K1R_FLUSH_PATH
-#define K1R_FLUSHOPS_OUT
-#define K1R_FLUSHOPS_IN
-#endif
-// SNAPPY_K1R_X5_INLOOP: a tag collision (the verification found fewer than 4
+// K1R_X5_PATH: a tag collision (the verification found fewer than 4
 // equal bytes: 27 rounds of a 32 KiB text unit) finishes as a miss inside K1r's
 // statement instead of leaving with code 5.  _x5 is the C++ code-5 branch in
 // scalar code: the skip fix first (the pending flag is still the previous
-// round's: this round's K1R_DK_LATE has not run), no deferred token, the inserts
+// round's: this round's dkn = 1 has not run), no deferred token, the inserts
 // of lanes lane0 - 1 .. lane0 and fresh entry reads when the collision was on the
 // round's first probe lane (the round inserted lane f alone then), p, skip and
 // lane0 as after a miss at f, and the miss round's way on.  K1r64's statement
-// keeps the exit (K1R_X5_EXIT).  SNAPPY_K1R_X5_INLOOP 0 is the parent's flow.
-#ifndef SNAPPY_K1R_X5_INLOOP
-#define SNAPPY_K1R_X5_INLOOP 1
-#endif
+// keeps the exit (K1R_X5_EXIT).
 #define K1R_X5_EXIT "L%=_x5:\n\ts_mov_b32 %[code], 5\n"
 #define K1R_X5_PATH                                                                                 \
     "L%=_x5:\n\t"                                                                                   \
@@ -1256,11 +1176,6 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_sub_u32 %[lane0], %[p], %[q0]\n\t"                                                           \
     K1R_NOHIT_TAIL("")                                                                              \
     "s_branch L%=_x3\n"
-#if SNAPPY_K1R_X5_INLOOP
-#define K1R_X5_32 K1R_X5_PATH
-#else
-#define K1R_X5_32 K1R_X5_EXIT
-#endif
 #define K1R_WIN_NONE "L%=_win:\n"
 #define K1R_WIN_STEP(dst)                                                                          \
     "v_add_u32_dpp %[t1], %[t1], %[pdl1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
@@ -1274,8 +1189,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "L%=_win:\n\t"                                                                                  \
     K1R_SKIPFIX                                                                                     \
     "s_add_u32 %[s0], %[pend], %[dkn]\n\t"                                                          \
-    "s_cmp_gt_u32 %[s0], 48\n\t" /* a token flush is due: K1R_FLUSH_PATH, or the C++ refresh */     \
-    "s_cbranch_scc1 L%=" K1R_FLUSH_TARGET "\n"                                                      \
+    "s_cmp_gt_u32 %[s0], 48\n\t" /* a token flush is due: K1R_FLUSH_PATH */                         \
+    "s_cbranch_scc1 L%=_fl\n"                                                                       \
     "L%=_wr:\n\t"                                                                                   \
     "s_add_u32 %[q0], %[p], -1\n\t"                                                                 \
     "s_lshr_b32 %[s0], %[q0], 8\n\t"                                                                \
@@ -1335,10 +1250,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_cbranch_scc1 L%=_x3\n\t"                                                                     \
     "s_branch L%=_top\n"                                                                            \
     K1R_FLUSH_PATH
-static_assert(SNAPPY_K1R_DMAX == 13 || !SNAPPY_K1R_WIN_INLOOP, "K1R_WIN_PATH is written out for DMAX 13");
-static_assert(SNAPPY_K1R_WIN_INLOOP || !SNAPPY_K1R_FLUSH_INLOOP, "K1R_FLUSH_PATH falls into K1R_WIN_PATH's refresh");
-static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
-              "K1R_FLUSH_PATH: one segment record per flush at most, its lane (0 - nt) & 255");
+static_assert(SNAPPY_K1R_DMAX == 13, "K1R_WIN_PATH is written out for DMAX 13");
+static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at most, its lane (0 - nt) & 255");
 // the window state: read only (K1R_WINOPS_IN) or moved by the _win path
 #define K1R_WINOPS_NONE_OUT
 #define K1R_WINOPS_NONE_IN(SEGHI)                                                                   \
@@ -1348,11 +1261,12 @@ static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
     [word] "v"(word),
 #define K1R_WINOPS_PATH_OUT                                                                         \
     , [q0] "+s"(q0), [mwin] "+s"(m_win), [lim0] "+s"(lim0), [dv] "+v"(dv), [hv] "+v"(hv), [pdl1] "+v"(pdl1), \
-      [pdc] "+v"(pdc), [pdnz] "+v"(pdnz), [adr] "+v"(adr), [adrt] "+v"(adrt), [word] "+v"(word) K1R_FLUSHOPS_OUT
+      [pdc] "+v"(pdc), [pdnz] "+v"(pdnz), [adr] "+v"(adr), [adrt] "+v"(adrt), [word] "+v"(word),              \
+      [nt] "+s"(nt), [acc] "+s"(acc), [cend] "+s"(cend) /* the flush */
 #define K1R_WINOPS_PATH_IN(SEGHI)                                                                   \
     [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),    \
-    K1R_FLUSHOPS_IN
-#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, HIT, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5) \
+    [tokb] "s"(tok), [segb] "s"(segu), /* the flush */
+#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5) \
     do {                                                                                            \
         uint32_t _m0s, _pf, _s0, _s1, _s2, _s3, _t0, _t1, _t2, _t3, _t4;                            \
         uint64_t _valid, _hm;                                                                       \
@@ -1362,13 +1276,14 @@ static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
             "s_cbranch_scc1 L%=_x3\n"                                                               \
             DUAL_SEL                                                                                \
             K1R_LOOP_PLACE(PAD)                                                                     \
-            K1R_ROUND_BODY(CAND, HIT, "")                                                           \
+            K1R_ROUND_BODY(CAND, "")                                                                \
             DUAL_LOOP                                                                               \
             "L%=_x3:\n\ts_mov_b32 %[code], 3\n\ts_branch L%=_end\n"                                 \
             "L%=_x1:\n\ts_mov_b32 %[code], 1\n\ts_branch L%=_end\n"                                 \
             WIN                                                                                     \
             "L%=_x2:\n\ts_mov_b32 %[code], 2\n\ts_branch L%=_end\n"                                 \
-            "L%=_x4:\n\t" K1R_X4                                                                   \
+            "L%=_x4:\n\t" /* the length test's two rare ends, told apart */                         \
+            "s_cmp_lt_u32 %[s0], 4\n\ts_cbranch_scc1 L%=_x5\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n" \
             "L%=_far:\n\t" /* K1r64: the candidate's 256 bytes from the input */                    \
             "s_and_b32 %[s1], %[c], -4\n\t"                                                         \
             "v_add_u32_e32 %[t1], %[s1], %[lane4]\n\t"                                              \
@@ -1499,20 +1414,15 @@ static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
                     rs_gopen = false;
 #endif
                     if constexpr (BIG) {
-                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND64, K1R_SEGHI64(seg_hi), K1R_HIT64, SNAPPY_K1R_PAD64,
+                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND64, K1R_SEGHI64(seg_hi), SNAPPY_K1R_PAD64,
                                             K1R64_HALF_SEL, K1R64_HALF_LOOP, K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN,
                                             K1R_X5_EXIT);
                     } else {
-#if SNAPPY_K1R_WIN_INLOOP
                         // (m_win17 is read by the C++ round alone: made there from q0 and L)
                         int32_t lim0 = __builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0);
                         uint32_t adrt = adr >> 1;
-                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
-                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN, K1R_X5_32);
-#else
-                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), K1R_HIT32, SNAPPY_K1R_PAD32, "", "",
-                                            K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN, K1R_X5_32);
-#endif
+                        K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), SNAPPY_K1R_PAD32, "", "",
+                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN, K1R_X5_PATH);
                     }
 #ifdef SNAPPY_K1R_RSTAMPS
                     RSTAMP(ra1);
@@ -1586,7 +1496,7 @@ static_assert(kK2Seg == 256 || !SNAPPY_K1R_FLUSH_INLOOP,
                     const uint32_t kcap = 64 - skip;
                     valid = ((2ull << kcap) - 1) << lane0;
                     uint64_t mw17 = m_win17;
-#if K1R_ASM_ROUNDS && SNAPPY_K1R_WIN_INLOOP
+#if K1R_ASM_ROUNDS
                     if constexpr (!BIG)  // the window may have moved inside the asm statement
                         mw17 = __ballot((int32_t)lane <= (int32_t)(L - 17 - q0) && lane <= 62);
 #endif
@@ -2042,28 +1952,21 @@ __device__ __forceinline__ void k2_long_literals(uint8_t *w, const uint8_t *__re
     }
 }
 
-// SNAPPY_K2_PREFETCH: token words one pass ahead (see the pass loop)
-// (A/B on 1 GiB, outputs identical, profiles/r05u_ab_k2_prefetch_*: K3 + K2 per
-// GiB 0.932-0.936 -> 0.910-0.911 ms on 32 KiB streams, 0.900-0.902 -> 0.861-0.864
-// on 64 KiB blocks with the register cap below; uncapped it needs 82 VGPRs, 5
-// waves per SIMD, and is slower: 0.984-0.985)
-#ifndef SNAPPY_K2_PREFETCH
-#define SNAPPY_K2_PREFETCH 1
-#endif
+// The token words are loaded one pass ahead (see the pass loop): A/B on 1 GiB,
+// outputs identical, profiles/r05u_ab_k2_prefetch_*: K3 + K2 per GiB 0.932-0.936
+// -> 0.910-0.911 ms on 32 KiB streams, 0.900-0.902 -> 0.861-0.864 on 64 KiB
+// blocks with the register cap of 6 waves per SIMD (80 VGPRs, the occupancy
+// before the prefetch); uncapped it needs 82 VGPRs, 5 waves per SIMD, and is
+// slower: 0.984-0.985.  Capping at 7 or 8 waves spills and measured slower
+// (1.18 / 1.22 against 0.979 ms of K3 + K2 per GiB of text).
+//
 // measurement only (wrong output): K2 reads no literal bytes from the input, the
 // upper bound of what literals staged by K1r could save K2
 #ifndef SNAPPY_K2_NOLIT
 #define SNAPPY_K2_NOLIT 0
 #endif
-// 1: no register cap (80 VGPRs, 6 waves/SIMD with 128-token passes); capping at
-// 7 or 8 waves spills and measured slower (1.18 / 1.22 against 0.979
-// ms of K3 + K2 per GiB of text)
-// (with the prefetch: 6, i.e. 80 VGPRs, the same occupancy as before it)
-#ifndef SNAPPY_K2_WAVES_PER_EU
-#define SNAPPY_K2_WAVES_PER_EU (SNAPPY_K2_PREFETCH ? 6 : 1)
-#endif
 #if SNAPPY_TU_COMPRESS
-__global__ __launch_bounds__(64, SNAPPY_K2_WAVES_PER_EU) void k2_emit_units(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit,
+__global__ __launch_bounds__(64, 6) void k2_emit_units(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit,
                                                     uint32_t hdr_mode, uint64_t header_value,
                                                     const uint2 *__restrict__ tokens, uint32_t tok_cap,
                                                     const uint32_t *__restrict__ ntok,
@@ -2086,7 +1989,6 @@ __global__ __launch_bounds__(64, SNAPPY_K2_WAVES_PER_EU) void k2_emit_units(cons
         if (hdr_mode == SNAPPY_HDR_EVERY_UNIT) varint_put(L, dst, lane);
         else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && u == 0) varint_put(header_value, dst, lane);
     }
-#if SNAPPY_K2_PREFETCH
     // the next pass's token words (and the next segment's record) are loaded one
     // pass ahead, so their round trip overlaps this pass's literal loads
     uint32_t kwn[kK2Per];
@@ -2102,16 +2004,11 @@ __global__ __launch_bounds__(64, SNAPPY_K2_WAVES_PER_EU) void k2_emit_units(cons
     };
     if (blockIdx.y * kK2Seg <= nt) load_kw(blockIdx.y * kK2Seg, kwn);
     uint2 sen = load_se(blockIdx.y);
-#endif
     for (uint32_t sg = blockIdx.y; sg * kK2Seg <= nt; sg += gridDim.y) {
     // K1r's table: the segment's output offset and the input position where
     // its first literal starts (the end of the previous segment's last token)
-#if SNAPPY_K2_PREFETCH
     const uint2 se = sen;
     sen = load_se(sg + gridDim.y);
-#else
-    const uint2 se = *reinterpret_cast<const uint2 *>(seg_off + 2 * ((uint64_t)u * segs + sg));
-#endif
     uint32_t o = se.x, carry = se.y;
     for (uint32_t c = sg * kK2Seg; c < (sg + 1) * kK2Seg && c <= nt; c += kK2Pass) {
 
@@ -2121,7 +2018,6 @@ __global__ __launch_bounds__(64, SNAPPY_K2_WAVES_PER_EU) void k2_emit_units(cons
     // the lane's token words in one round trip (a lane past the end re-reads word 0:
     // no branch, so no load waits for the one before it), then the rare escapes
     uint32_t kw[kK2Per];
-#if SNAPPY_K2_PREFETCH
 #pragma unroll
     for (uint32_t i = 0; i < kK2Per; i++) kw[i] = kwn[i];
     {
@@ -2129,13 +2025,6 @@ __global__ __launch_bounds__(64, SNAPPY_K2_WAVES_PER_EU) void k2_emit_units(cons
         if (!(cn < (sg + 1) * kK2Seg && cn <= nt)) cn = (sg + gridDim.y) * kK2Seg;
         if (cn <= nt) load_kw(cn, kwn);
     }
-#else
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) {
-        const uint32_t t = c + kK2Per * lane + i;
-        kw[i] = tok[t < nt ? t : 0u];
-    }
-#endif
 #pragma unroll
     for (uint32_t i = 0; i < kK2Per; i++) {
         const uint32_t t = c + kK2Per * lane + i;
@@ -2675,14 +2564,6 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
     uint32_t n_half = 0, n_E = 0, n_cut_bad = 0, n_cut_long = 0, n_cut_span = 0, n_full = 0, n_spanb = 0;
     uint32_t n_stop_win = 0;  // batches whose halves stopped at the window limit (E < 64)
 #endif
-#ifndef SNAPPY_K4_SPAN_ADAPT
-#define SNAPPY_K4_SPAN_ADAPT 1
-#endif
-// SNAPPY_K4_JSIZE: the batch parse's jumps take a long literal (m >= 60) as
-// leaving the 64 positions; only the last element's exact size is computed
-#ifndef SNAPPY_K4_JSIZE
-#define SNAPPY_K4_JSIZE 0
-#endif
     // the last batch was cut by the 1,024-byte output span (long copies): parse one
     // half only -- more elements would be cut again (repeat-like data)
     bool span_cut = false;
@@ -2728,22 +2609,10 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
                 // element size: literal 1 + k + (length - 1) + 1, copies 2 / 3 / 5
                 // (src/snappy_decompression.c:290-333)
                 const uint32_t tag = x0 & 0xFF, m = tag >> 2, t = tag & 3;
-#if SNAPPY_K4_JSIZE == 2
-                const uint32_t k = __builtin_elementwise_sub_sat(m, 59u);
-                const uint32_t lv = k ? b4 & (0xFFFFFFFFu >> ((32 - 8 * k) & 31)) : m;
-                const uint32_t xsize = t == 0 ? __builtin_elementwise_add_sat(lv, k + 2) : (0x5320u >> (4 * t)) & 0xF;
-                const uint32_t size = t == 0 ? (m < 60 ? m + 2 : 64u) : (0x5320u >> (4 * t)) & 0xF;
-#elif SNAPPY_K4_JSIZE
-                // for the jumps only: a literal with m >= 60 is >= 63 bytes, taken as
-                // leaving the 64 (at lane 0 it may end at 63: the half then ends one
-                // element early, and the next starts at its exact end, hexit below)
-                const uint32_t size = t == 0 ? (m < 60 ? m + 2 : 64u) : (0x5320u >> (4 * t)) & 0xF;
-#else
                 const uint32_t k = __builtin_elementwise_sub_sat(m, 59u);
                 const uint32_t lv = k ? b4 & (0xFFFFFFFFu >> ((32 - 8 * k) & 31)) : m;
                 // (saturating: a 4-byte length of 2^32 - 1 .. 2^32 - 6 must not wrap to a small size)
                 const uint32_t size = t == 0 ? __builtin_elementwise_add_sat(lv, k + 2) : (0x5320u >> (4 * t)) & 0xF;
-#endif
                 // positions as ds_bpermute addresses (4 x position); one >= 256 has
                 // left the 64 and must stay >= 256 (its exact value is never used).
                 // Every jump goes forward (an element is >= 2 bytes: T[a / 4] > a for
@@ -2775,22 +2644,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
                 // (with a saturated size, last + 0xFFFFFFFF wraps to last - 1: a further half may
                 // then be parsed from inside this one.  Harmless: its garbage elements take lanes
                 // after the oversized literal, which is refused as TRUNCATED, and nexec cuts there)
-#if SNAPPY_K4_JSIZE == 2
-                hexit = last + (uint32_t)__builtin_amdgcn_readlane(xsize, last);
-#elif SNAPPY_K4_JSIZE
-                {  // the last element's exact size, in scalar registers
-                    const uint32_t lx = (uint32_t)__builtin_amdgcn_readlane(x0, last);
-                    const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane(b4, last);
-                    const uint32_t ltag = lx & 0xFF, lm = ltag >> 2, lt = ltag & 3;
-                    uint32_t lk;  // max(m, 59) - 59 in scalar code (the compiler's saturating form is VALU)
-                    asm("s_max_u32 %0, %1, 59" : "=s"(lk) : "s"(lm) : "scc");
-                    lk -= 59;
-                    const uint32_t llv = lk ? lb & (0xFFFFFFFFu >> ((32 - 8 * lk) & 31)) : lm;
-                    hexit = last + (lt == 0 ? __builtin_elementwise_add_sat(llv, lk + 2) : (0x5320u >> (4 * lt)) & 0xF);
-                }
-#else
                 hexit = last + (uint32_t)__builtin_amdgcn_readlane(size, last);
-#endif
             };
             uint32_t ax0, ab4, ea, xa;
             parse_half(o, ax0, ab4, ea, xa);
@@ -2819,7 +2673,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
 #ifdef SNAPPY_K4_STATS
                 n_stop_win += (E < 64 && hpos > 440 && !span_cut) ? 1u : 0u;
 #endif
-                if (!(E < 64 && hpos <= 440) || (SNAPPY_K4_SPAN_ADAPT && span_cut)) break;
+                if (!(E < 64 && hpos <= 440) || span_cut) break;
 #ifdef SNAPPY_K4_STATS
                 n_half++;
 #endif

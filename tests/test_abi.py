@@ -119,6 +119,36 @@ def test_wrong_output_knobs_refuse_to_compile(tmp_path):
         assert r.returncode != 0 and "measurement builds only" in r.stderr, (knob, r.stderr[-2000:])
 
 
+def test_variant_build_links_the_product_objects(tmp_path):
+    """The Makefile is the only build recipe: a variant library (tools/build_prev.sh,
+    tools/build_pads.sh: `make lib` with the variant variables) links the objects
+    the product links, so a new object cannot be left out of the A/B builds."""
+    import shutil
+    pkg = os.path.join(ROOT, "lightweight-snappy_amd")
+
+    def link_objects(*args):  # dry run: nothing is compiled
+        out = subprocess.run(["make", "-n", "-B", "-C", pkg, *args], check=True, capture_output=True, text=True).stdout
+        links = [ln.split() for ln in out.splitlines() if " -shared " in ln and ".o " in ln + " "]
+        assert len(links) == 1, out
+        return sorted(os.path.basename(w) for w in links[0] if w.endswith(".o")), out
+
+    product, _ = link_objects()
+    shutil.copytree(os.path.join(pkg, "csrc"), tmp_path / "csrc")  # (a revision's sources, as build_prev.sh unpacks them)
+    shutil.copytree(INC, tmp_path / "include")
+    variant, out = link_objects("lib", f"SRCDIR={tmp_path}/csrc", f"INCDIR={tmp_path}/include", f"OBJDIR={tmp_path}/obj",
+                                f"LIBOUT={tmp_path}/libsnappy_amd_x.so", "DEFS_COMPRESS=-DSNAPPY_K1R_PAD32=3",
+                                "DEFS_DECODE=-DSNAPPY_K4_HALVES=2", "DEFS_SHIM=-DSNAPPY_K2_WAVES=4u",
+                                "SCHED_COMPRESS=-DSCHED_C_HERE", "SCHED_DECODE=-DSCHED_D_HERE")
+    assert len(product) >= 8 and variant == product, (product, variant)
+    # and the variables reach the commands they are for
+    cmds = {w[w.index("-o") + 1].rsplit("/", 1)[-1]: " ".join(w) for w in map(str.split, out.splitlines()) if "-o" in w}
+    assert "-DSNAPPY_K1R_PAD32=3" in cmds["snappy_kernels_c.o"] and "-DSCHED_C_HERE" in cmds["snappy_kernels_c.o"]
+    assert "-DSNAPPY_K4_HALVES=2" in cmds["snappy_kernels_d.o"] and "-DSCHED_D_HERE" in cmds["snappy_kernels_d.o"]
+    for shim in ("snappy_device.o", "snappy_frame.o"):
+        assert "-DSNAPPY_K2_WAVES=4u" in cmds[shim], cmds[shim]
+    assert all(f"{tmp_path}/csrc/" in c for o, c in cmds.items() if o.endswith(".o"))
+
+
 @pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference sources only in the build container")
 def test_reference_cli_links_against_library(tmp_path):
     # the reference's own src/cmd.c, unchanged, links against libsnappy_amd.so

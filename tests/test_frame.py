@@ -151,6 +151,59 @@ def test_compress_frame_host_buffer(kind, n):
     assert snappy_amd.compress_frame(a.tobytes()) == want
 
 
+# ---- compress, the scan's two kernels ---------------------------------------
+# The shared compress launch picks K3: one wave up to 8,192 units, the block scan
+# from 8,193 on.  A chunk is 65,536 bytes, so these are the smallest framed
+# inputs on either side of that choice; everything is compared on the device.
+K3_WAVE_MAX = 8192
+
+
+@pytest.fixture(scope="module")
+def big_text():
+    x = torch.from_numpy(datagen.make("T", K3_WAVE_MAX * CH + 1, 2468)).cuda()
+    yield x
+    del x
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("units", [K3_WAVE_MAX, K3_WAVE_MAX + 1])
+def test_compress_frame_at_the_scan_kernel_threshold(codec, big_text, units):
+    n = K3_WAVE_MAX * CH + (units - K3_WAVE_MAX)
+    x = big_text[:n]
+    assert (n + CH - 1) // CH == units
+    i64 = dict(dtype=torch.int64, device="cuda")
+    try:
+        frame, chunks = codec.compress_frame_tensor(x)
+        payload, offs = codec.compress_tensor(x, chunk=CH, layout=snappy_amd.STREAMS)
+        # the chunk table: header u lies 10 + 8 u bytes further than stream u; the last entry closes the frame
+        assert chunks.numel() == units + 1 and offs.numel() == units + 1
+        assert torch.equal(chunks, offs + 10 + 8 * torch.arange(units + 1, **i64))
+        assert int(chunks[-1]) == frame.numel() <= snappy_amd.max_frame_output(n)
+        # the headers: type 00, 24-bit length = CRC + payload, masked CRC-32C of the chunk's input
+        hdr = frame[chunks[:-1, None] + torch.arange(8, **i64)].to(torch.int64)
+        assert not hdr[:, 0].any()
+        assert torch.equal(hdr[:, 1] | hdr[:, 2] << 8 | hdr[:, 3] << 16, 4 + offs[1:] - offs[:-1])
+        start = CH * torch.arange(units, **i64)
+        off_len = torch.stack([start, torch.clamp(n - start, max=CH)], dim=1).contiguous()
+        crc = codec.crc32c_tensor(x, off_len, masked=True).to(torch.int64) & 0xFFFFFFFF
+        assert torch.equal(hdr[:, 4] | hdr[:, 5] << 8 | hdr[:, 6] << 16 | hdr[:, 7] << 24, crc)
+        del hdr, crc, off_len, start
+        # without the identifier and the headers, the frame is the STREAMS payload (512 chunks at a time)
+        table, soffs = chunks.cpu().tolist(), offs.cpu().tolist()
+        for a in range(0, units, 512):
+            b = min(a + 512, units)
+            piece = frame[table[a]:table[b]]
+            keep = torch.ones(piece.numel(), dtype=torch.bool, device="cuda")
+            keep[(chunks[a:b, None] - table[a] + torch.arange(8, **i64)).reshape(-1)] = False
+            assert torch.equal(piece[keep], payload[soffs[a]:soffs[b]]), (a, b)
+        assert frame[:10].cpu().numpy().tobytes() == fm.IDENTIFIER
+        del payload, piece, keep
+        back = codec.decompress_frame_tensor(frame, chunks, n)
+        assert torch.equal(back, x)
+    finally:
+        codec.trim()  # (the scratch of 8,193 units is over a GiB: not kept for the session's later tests)
+
+
 # ---- decode, own streams ----------------------------------------------------
 @pytest.mark.parametrize("kind,n", CASES)
 def test_round_trip_device_and_buffer(codec, kind, n):

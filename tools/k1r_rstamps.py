@@ -6,8 +6,10 @@ one group of exits (from the statement's end to the first useful instruction
 outside, from the last one back to the statement).  The build picks the group
 with -DSNAPPY_K1R_RSTAMPS_GROUP=: 1 code-2 refreshes without a token flush,
 2 code-2 refreshes with one, 4 / 5 the code-4 / code-5 exits that come back.
--DSNAPPY_K1R_WIN_INLOOP=0, -DSNAPPY_K1R_FLUSH_INLOOP=0 and
--DSNAPPY_K1R_X5_INLOOP=0 build the flows in which those exits still happen.
+K1r refreshes, flushes and finishes tag collisions inside its statement (it
+leaves with code 2 only for a flush that holds a long-form token, never with
+code 5): the refresh-by-exit groups are measured on K1r64 (CHUNK 65536), whose
+statement keeps those exits.
 Usage: tools/k1r_rstamps.py BYTES CHUNK [VARIANT [GROUP]]
 (VARIANT: tools/build_pads.sh 'rst:-DSNAPPY_K1R_RSTAMPS'; GROUP: the group the
 variant was built with, for the label)"""

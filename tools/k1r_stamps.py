@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-segment cycle shares of the K1r round (SNAPPY_K1R_STAMPS build)."""
+"""Per-segment cycle shares of the K1r round (SNAPPY_K1R_LSTAMPS build, variant
+"stamps": tools/build_pads.sh 'stamps:-DSNAPPY_K1R_LSTAMPS')."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lightweight-snappy_amd"))

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""A/B the kernel variants built by tools/variants.sh in ONE process each,
+"""A/B the library variants built by tools/build_prev.sh or tools/build_pads.sh
+(lightweight-snappy_amd/variants/; "default" is the tree's library) in ONE process each,
 interleaved rounds: K1/K3/K4 HIP-event times on the same seeded workload,
 output bytes checked identical across variants (sha256)."""
 import argparse
