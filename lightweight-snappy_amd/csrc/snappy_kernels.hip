@@ -861,14 +861,15 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // With the window refresh inside K1r's statement (profiles/r08b_*): PAD32 0..15 ->
 // 11.12-11.14 (2 and 10) to 11.46-11.49 (15) ms per GiB, the parent 11.91-11.92.
 #ifndef SNAPPY_K1R_PAD32
-#define SNAPPY_K1R_PAD32 2  // with the window refresh inside the statement (profiles/r08b_*), and again with the
-                            // flush and the tag-collision round inside it (r09b_*: 2 and 10 best of 0..15)
+#define SNAPPY_K1R_PAD32 8  // 2 with the window refresh inside the statement (profiles/r08b_*) and with the flush
+                            // and the tag-collision round inside it (r09b_*); 8 with the hit tail's direct way
+                            // into the refresh and its length test against 4 (r15c_*: 8 and 0 best of 0..15)
 #endif
 #ifndef SNAPPY_K1R_PAD64
 #define SNAPPY_K1R_PAD64 0  // with K1r64's first-32-KiB loop, K1R64_HALF_LOOP (profiles/r06aa_*, r06ad_*)
 #endif
-#ifndef SNAPPY_K1R_PAD64A  // K1r64's first-32-KiB loop (-1 with the early token offset, r06ah_*)
-#define SNAPPY_K1R_PAD64A -1
+#ifndef SNAPPY_K1R_PAD64A  // K1r64's first-32-KiB loop (-1 with the early token offset, r06ah_*; 0 with the
+#define SNAPPY_K1R_PAD64A 0 // length test against 4 alone, r15e_*: best of -1, 0..14 even)
 #endif
 #define K1R_STR2(x) #x
 #define K1R_STR(x) K1R_STR2(x)
@@ -917,18 +918,24 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // One round loop of the asm statement (labels suffixed with T).
 // The token offset: a hit round's dkb = pf - c is written right after the drain
 // that consumed the previous one (in the gather wait's shadow), not on the tail
-// after the length read-back.  (The pending flag dkn stays on the tail: the tag
-// collision's skip fix reads the previous round's.)  A/B, outputs identical,
+// after the length read-back.  A/B, outputs identical,
 // 68 GPU tests green, at each build's best placements (profiles/r06ag_*, r06ah_*):
 // K1r 12.11-12.13 -> 12.04-12.08 ms per GiB, K1r64 13.55-13.60 -> 13.49-13.51.
+// The pending flag dkn stays on the tail: the tag collision's skip fix reads the
+// previous round's.  Set behind the drain as well, with that fix on pend - m0 (the
+// drain leaves m0 = pend before it), it measured 0.3 % faster in K1r and 0.5 %
+// slower in K1r64, each at its best placement (profiles/r15e_*): not kept.
 // The match length: lane s1 (the first differing dword of the 64 bytes, -1 if
-// none in lanes 0-31) gives 4 s1 + the byte.  One unsigned test of len - 4 > 59
-// leaves for both rare ends (>= 64 equal bytes: s1 > 15, or -1, whose lane 63
-// reads >= 252; a tag collision: len < 4), told apart at _x4: one compare and
-// one branch fewer per hit round than a test for each, K1r 12.18-12.24 ->
-// 12.11-12.17 ms per GiB and K1r64 13.94-13.98 -> 13.82-13.86, each at its best
-// loop placement (profiles/r06x_*, r06y_*, outputs identical)
-#define K1R_ROUND_BODY(CAND, T)                                                                     \
+// none in lanes 0-31) gives 4 s1 + the byte.  The tail tests it once, len < 4 (a
+// tag collision, to _x5), before it writes lane0 = f + len.  64 or more equal
+// bytes (s1 > 15, or -1, whose lane 63 reads >= 252) need no test there: f + len
+// is past every lim0 (<= 62 - RMIN), so such a round takes the leaving path, whose
+// first compare sends it to _x4 (code 4; the C++ handler reads fx, cx, q0 and L
+// and writes dka, dkb, dkn, skip, p and lane0 anew).  LEAVE is what a kernel puts
+// in front of the clamp to the block end (K1r: K1R_LEAVE_WIN; K1r64: nothing).
+// Before: one unsigned test of len - 4 > 59 for both rare ends, told apart at _x4
+// (profiles/r06x_*, r06y_*); the compare against 4 saves the s_add (profiles/r15c_*).
+#define K1R_ROUND_BODY(CAND, T, LEAVE)                                                                   \
             "L%=_top" T ":\n\t"                                                                          \
             "s_lshl_b64 %[valid], %[dmask], %[lane0]\n\t"                                           \
             "v_cmp_gt_i32_e32 vcc, %[lane0], %[pdl1]\n\t" /* vcc = not in-round */                  \
@@ -973,15 +980,17 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "v_lshl_or_b32 %[t2], %[lane], 2, %[t2]\n\t" /* the prefix length if this dword differs */ \
             "s_ff1_i32_b32 %[s1], vcc_lo\n\t"                                                       \
             "v_readlane_b32 %[s0], %[t2], %[s1]\n\t" /* len */                                      \
-            "s_add_u32 %[s2], %[s0], -4\n\t"                                                        \
-            "s_cmp_gt_u32 %[s2], 59\n\t"                                                            \
-            "s_cbranch_scc1 L%=_x4\n\t" /* >= 64 equal bytes, or a tag collision */                 \
+            "s_cmp_lt_u32 %[s0], 4\n\t"                                                             \
+            "s_cbranch_scc1 L%=_x5\n\t" /* a tag collision */                                       \
             "s_add_u32 %[lane0], %[f], %[s0]\n\t"                                                   \
             "s_pack_ll_b32_b16 %[dka], %[pf], %[s0]\n\t"                                           \
             "s_mov_b32 %[dkn], 1\n\t"                                                               \
-            "s_cmp_le_i32 %[lane0], %[lim0]\n\t" /* implies pf + len <= L - 16: no clamp */         \
+            "s_cmp_le_i32 %[lane0], %[lim0]\n\t" /* implies len < 64 and pf + len <= L - 16 */      \
             "s_cbranch_scc1 L%=_top" T "\n\t"                                                            \
-            "s_sub_u32 %[s2], %[L], %[pf]\n\t" /* leaving: the length clamped to the block end */ \
+            "s_cmp_gt_u32 %[s0], 63\n\t" /* leaving: >= 64 equal bytes (lane0 > 63 > lim0) */       \
+            "s_cbranch_scc1 L%=_x4\n\t"                                                             \
+            LEAVE                                                                                   \
+            "s_sub_u32 %[s2], %[L], %[pf]\n\t" /* the length clamped to the block end */          \
             "s_min_u32 %[s0], %[s0], %[s2]\n\t"                                                     \
             "s_add_u32 %[p], %[pf], %[s0]\n\t"                                                      \
             "s_sub_u32 %[lane0], %[p], %[q0]\n\t"                                                   \
@@ -1018,7 +1027,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // r06ad_*); random and repeat equal
 #define K1R64_HALF_SEL "s_cmp_eq_u32 %[seghi], 0\n\ts_cbranch_scc1 L%=_topa\n"
 // (the first loop's miss path falls through to the code-3 exit: branch there)
-#define K1R64_HALF_LOOP "s_branch L%=_x3\n" K1R_LOOP_PLACE(SNAPPY_K1R_PAD64A) K1R_ROUND_BODY(K1R_CAND32, "a")
+#define K1R64_HALF_LOOP "s_branch L%=_x3\n" K1R_LOOP_PLACE(SNAPPY_K1R_PAD64A) K1R_ROUND_BODY(K1R_CAND32, "a", "")
 // K1R_WIN_PATH: K1r's window refresh as a path of the statement (_win)
 // instead of a code-2 exit, the C++ WINDOW_LS and a re-entry, when no token
 // flush is due (pend + dkn <= 48: 444 of a 32 KiB text unit's 518 refreshes).
@@ -1177,6 +1186,21 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     K1R_NOHIT_TAIL("")                                                                              \
     "s_branch L%=_x3\n"
 #define K1R_WIN_NONE "L%=_win:\n"
+// K1R_LEAVE_WIN: a hit that ends K1r's window goes straight to the refresh.
+// lane0 > lim0 and len < 64 here; p = q0 + lane0 is pf + len.  Unless that
+// passes L - 16 (the clamp and its code-1 test, which write p anew) nothing is
+// left of the generic way through _win but what a hit makes known: the length
+// stands as packed into dka, lane0 stands, the pending flag is 1, so skip is 32
+// and a flush is due when pend > 47.
+#define K1R_LEAVE_WIN                                                                               \
+    "s_add_u32 %[p], %[q0], %[lane0]\n\t"                                                           \
+    "s_cmp_gt_u32 %[p], %[lm16]\n\t"                                                                \
+    "s_cbranch_scc1 L%=_clamp\n\t"                                                                  \
+    "s_mov_b32 %[skip], 32\n\t"                                                                     \
+    "s_cmp_gt_u32 %[pend], 47\n\t"                                                                  \
+    "s_cbranch_scc1 L%=_fl\n\t"                                                                     \
+    "s_branch L%=_wr\n"                                                                             \
+    "L%=_clamp:\n\t"
 #define K1R_WIN_STEP(dst)                                                                          \
     "v_add_u32_dpp %[t1], %[t1], %[pdl1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
     "v_bitop3_b32 " dst ", %[t0], %[t1], %[s0] bitop3:0x6c\n\t" /* shifted ^ (w & 0xFFFF0000) */
@@ -1266,7 +1290,7 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
 #define K1R_WINOPS_PATH_IN(SEGHI)                                                                   \
     [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),    \
     [tokb] "s"(tok), [segb] "s"(segu), /* the flush */
-#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5) \
+#define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5, LEAVE) \
     do {                                                                                            \
         uint32_t _m0s, _pf, _s0, _s1, _s2, _s3, _t0, _t1, _t2, _t3, _t4;                            \
         uint64_t _valid, _hm;                                                                       \
@@ -1276,14 +1300,13 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
             "s_cbranch_scc1 L%=_x3\n"                                                               \
             DUAL_SEL                                                                                \
             K1R_LOOP_PLACE(PAD)                                                                     \
-            K1R_ROUND_BODY(CAND, "")                                                                \
+            K1R_ROUND_BODY(CAND, "", LEAVE)                                                             \
             DUAL_LOOP                                                                               \
             "L%=_x3:\n\ts_mov_b32 %[code], 3\n\ts_branch L%=_end\n"                                 \
             "L%=_x1:\n\ts_mov_b32 %[code], 1\n\ts_branch L%=_end\n"                                 \
             WIN                                                                                     \
             "L%=_x2:\n\ts_mov_b32 %[code], 2\n\ts_branch L%=_end\n"                                 \
-            "L%=_x4:\n\t" /* the length test's two rare ends, told apart */                         \
-            "s_cmp_lt_u32 %[s0], 4\n\ts_cbranch_scc1 L%=_x5\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n" \
+            "L%=_x4:\n\ts_mov_b32 %[code], 4\n\ts_branch L%=_end\n"                                 \
             "L%=_far:\n\t" /* K1r64: the candidate's 256 bytes from the input */                    \
             "s_and_b32 %[s1], %[c], -4\n\t"                                                         \
             "v_add_u32_e32 %[t1], %[s1], %[lane4]\n\t"                                              \
@@ -1416,13 +1439,13 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
                     if constexpr (BIG) {
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND64, K1R_SEGHI64(seg_hi), SNAPPY_K1R_PAD64,
                                             K1R64_HALF_SEL, K1R64_HALF_LOOP, K1R_WIN_NONE, K1R_WINOPS_NONE_OUT, K1R_WINOPS_NONE_IN,
-                                            K1R_X5_EXIT);
+                                            K1R_X5_EXIT, "");
                     } else {
                         // (m_win17 is read by the C++ round alone: made there from q0 and L)
                         int32_t lim0 = __builtin_elementwise_min((int32_t)(62 - SNAPPY_K1R_RMIN), (int32_t)L - 16 - (int32_t)q0);
                         uint32_t adrt = adr >> 1;
                         K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, K1R_CAND32, "i"(0), SNAPPY_K1R_PAD32, "", "",
-                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN, K1R_X5_PATH);
+                                            K1R_WIN_PATH, K1R_WINOPS_PATH_OUT, K1R_WINOPS_PATH_IN, K1R_X5_PATH, K1R_LEAVE_WIN);
                     }
 #ifdef SNAPPY_K1R_RSTAMPS
                     RSTAMP(ra1);
