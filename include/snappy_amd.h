@@ -148,7 +148,10 @@ void *snappy_amd_get_stream(snappy_amd_ctx *ctx);
 
 /* Device bytes the context holds as scratch (token lists, segment records,
  * status words, staging of the host-buffer path, index scratch); it grows to
- * the largest call made and is kept. */
+ * the largest call made and is kept.  A record batch (compress_records_device)
+ * of `count` records holding `total` bytes needs at most S + S/8 + 16,512 with
+ * S = 2 total + total/128 + 64 count + 256 (snappy_amd_max_records_scratch):
+ * linear in the bytes and in the count. */
 size_t snappy_amd_device_bytes(snappy_amd_ctx *ctx);
 /* Release the scratch above (synchronises the context stream); the next call
  * allocates again.  The status words of a decode whose status has not been
@@ -228,6 +231,72 @@ int snappy_amd_decompress_device_ex(snappy_amd_ctx *ctx, const void *d_comp, con
  * bytes or covers a boundary more than 2^24 - 1 bytes after its start. */
 int snappy_amd_index_device(snappy_amd_ctx *ctx, const void *d_comp, size_t clen, uint64_t *d_offsets,
                             size_t max_units, size_t *n_out);
+
+/* ---- record batches: many independent streams in one call ---------------- */
+/* A record is one raw Snappy stream (varint preamble, then elements) of
+ * 0..SNAPPY_AMD_RECORD_MAX decoded bytes; a batch is `count` records named by
+ * (offset, length) u64 pairs relative to one base pointer (the form
+ * snappy_amd_crc32c_device takes): any alignment, any order, gaps allowed --
+ * Parquet/ORC pages between their headers, RPC or log records, KV blocks.
+ * All three calls run on the context stream.
+ *
+ * Scratch: a compress call of `count` records holding `total` bytes grows
+ * snappy_amd_device_bytes() to at most snappy_amd_max_records_scratch(total,
+ * count) = S + S/8 + 16,512 with S = 2 total + total/128 + 64 count + 256:
+ * per record of L bytes 8 (L/4 + 2) bytes of tokens and escapes, 8 bytes per 256
+ * tokens of segment records and 32 bytes of plan tables, sizes and counts; the
+ * eighth and the constant are the slack of the four buffers.  Linear in the
+ * bytes and in the count -- not count * 65,536. */
+#define SNAPPY_AMD_RECORD_MAX 65536u
+/* Capacity d_out must have: total + total/32 + 32 count + 16 (per record the
+ * bound of a one-unit SNAPPY_AMD_STREAMS launch). */
+size_t snappy_amd_max_records_output(size_t total_bytes, size_t count);
+size_t snappy_amd_max_records_scratch(size_t total_bytes, size_t count);
+
+/* Compress record i = d_in[off_i, off_i + len_i) (d_in_off_len: count pairs,
+ * device).  A record of len >= 1 becomes exactly the bytes of snappy_compress()
+ * on it (the SNAPPY_AMD_STREAMS unit of chunk = len); len == 0 becomes the one
+ * byte 00.  The compressed records are packed back to back in d_out;
+ * d_offsets (count + 1 u64, device) gets each one's position and the total,
+ * *out_len (host) the total.  d_status (count i32, device; may be NULL) gets 0
+ * or the record's refusal: SNAPPY_AMD_ERR_UNSUPPORTED for len > 65,536,
+ * SNAPPY_AMD_ERR_ARG for a range that leaves [0, in_bytes).  A refused record
+ * writes 0 bytes, none of its bytes is loaded, and its neighbours are
+ * compressed as usual; the call returns the first refused record's status (0:
+ * none).  out_cap below snappy_amd_max_records_output(sum of the accepted
+ * lengths, count): SNAPPY_AMD_ERR_CAPACITY, nothing written.  Synchronises
+ * twice: for the plan's totals (which size the scratch) and for *out_len. */
+int snappy_amd_compress_records_device(snappy_amd_ctx *ctx, const void *d_in, size_t in_bytes,
+                                       const uint64_t *d_in_off_len, size_t count, void *d_out, size_t out_cap,
+                                       uint64_t *d_offsets, int32_t *d_status, size_t *out_len);
+
+/* Each record's declared length (its preamble: LEB128, the rules of
+ * snappy_varint_decode) into d_len[i]; d_status[i] (may be NULL) = 0,
+ * SNAPPY_AMD_ERR_HEADER for a malformed or cut preamble, SNAPPY_AMD_ERR_TRUNCATED
+ * for a range outside comp_bytes -- both with length 0.  A length above 65,536
+ * is returned as it is.  Asynchronous: returns once the kernel is queued. */
+int snappy_amd_records_length_device(snappy_amd_ctx *ctx, const void *d_comp, size_t comp_bytes,
+                                     const uint64_t *d_comp_off_len, size_t count, uint64_t *d_len,
+                                     int32_t *d_status);
+
+/* Decode record i from d_comp[comp_off_i, + comp_len_i) into d_out[out_off_i,
+ * + out_len_i).  Any valid stream of any writer; its preamble must equal
+ * out_len_i (SNAPPY_AMD_ERR_HEADER otherwise; records_length_device tells a
+ * caller that does not know).  A record's bytes and status are those of a
+ * one-unit snappy_amd_decompress_device(chunk = out_len_i, SNAPPY_AMD_STREAMS)
+ * on the same bytes; a copy reaching before the record's start is
+ * SNAPPY_AMD_ERR_OFFSET.  out_len_i == 0 needs the payload 00; an empty
+ * compressed range is SNAPPY_AMD_ERR_HEADER.  Checked before any byte of the
+ * record is loaded or stored: out_len_i > 65,536 SNAPPY_AMD_ERR_UNSUPPORTED, a
+ * compressed range outside comp_bytes SNAPPY_AMD_ERR_TRUNCATED, an output range
+ * outside out_bytes SNAPPY_AMD_ERR_CAPACITY.  A failing record may leave a
+ * prefix of its own output range written, never a byte outside it; overlapping
+ * output ranges are the caller's error.  d_status (count i32, device; may be
+ * NULL) gets every record's status (never a positive value).  sync = 1 waits
+ * and returns the first failing record's status, sync = 0 returns once queued. */
+int snappy_amd_decompress_records_device(snappy_amd_ctx *ctx, const void *d_comp, size_t comp_bytes,
+                                         const uint64_t *d_comp_off_len, size_t count, void *d_out, size_t out_bytes,
+                                         const uint64_t *d_out_off_len, int32_t *d_status, int sync);
 
 /* ---- Snappy framing format (framing_format.txt of google/snappy) -------- */
 /* The file format other Snappy tools exchange: the 10-byte stream identifier

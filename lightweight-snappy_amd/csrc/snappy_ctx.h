@@ -42,6 +42,9 @@ struct snappy_amd_ctx {
     // chunk records, unit index, status words) and the unframed payloads K4 decodes
     uint8_t *f_meta = nullptr; size_t f_meta_cap = 0;
     uint8_t *f_scr = nullptr; size_t f_scr_cap = 0;
+    // record batches (snappy_records.hip): the plan pass's tables and result words
+    // (the records' token scratch is `tokens`, their sizes and counts `sizes` / `ntok`)
+    uint8_t *r_meta = nullptr; size_t r_meta_cap = 0;
     bool timing = false;
     bool serial_index = false;  // SNAPPY_AMD_OPT_SERIAL_INDEX
     uint32_t k1r_extra_lds = 0; // SNAPPY_AMD_OPT_K1R_EXTRA_LDS

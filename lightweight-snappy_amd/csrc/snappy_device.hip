@@ -143,7 +143,7 @@ void snappy_amd_destroy(snappy_amd_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->sizes, c->tokens, c->ntok, c->seg_off, c->status, c->total, c->k5res,
-                    c->d_a, c->d_b, c->d_idx, c->k5buf, c->k5copy, c->f_meta, c->f_scr};
+                    c->d_a, c->d_b, c->d_idx, c->k5buf, c->k5copy, c->f_meta, c->f_scr, c->r_meta};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->h_total) (void)hipHostFree(c->h_total);
     if (c->h_status) (void)hipHostFree(c->h_status);
@@ -156,7 +156,7 @@ size_t snappy_amd_device_bytes(snappy_amd_ctx *c)
 {
     if (!c) return 0;
     return c->sizes_cap + c->tokens_cap + c->ntok_cap + c->seg_off_cap + c->status_cap + c->d_a_cap + c->d_b_cap +
-           c->d_idx_cap + c->k5buf_cap + c->k5copy_cap + c->f_meta_cap + c->f_scr_cap + 128;
+           c->d_idx_cap + c->k5buf_cap + c->k5copy_cap + c->f_meta_cap + c->f_scr_cap + c->r_meta_cap + 128;
 }
 
 int snappy_amd_trim(snappy_amd_ctx *c)
@@ -171,6 +171,7 @@ int snappy_amd_trim(snappy_amd_ctx *c)
         {reinterpret_cast<void **>(&c->d_idx), &c->d_idx_cap}, {reinterpret_cast<void **>(&c->k5buf), &c->k5buf_cap},
         {reinterpret_cast<void **>(&c->k5copy), &c->k5copy_cap},
         {reinterpret_cast<void **>(&c->f_meta), &c->f_meta_cap}, {reinterpret_cast<void **>(&c->f_scr), &c->f_scr_cap},
+        {reinterpret_cast<void **>(&c->r_meta), &c->r_meta_cap},
         // a decode's status words only once its status has been read (the result is kept)
         {reinterpret_cast<void **>(&c->status), c->status_pending ? nullptr : &c->status_cap}};
     for (auto &b : bufs) {

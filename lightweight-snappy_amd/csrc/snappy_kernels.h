@@ -70,6 +70,39 @@ __global__ void k4_decompress_back(const uint8_t *__restrict__ comp, const uint6
                                    uint64_t n, uint32_t unit, uint32_t hdr_mode, uint64_t header_value,
                                    uint32_t bias, uint8_t *__restrict__ out,
                                    int32_t *__restrict__ status);
+// ---- record batches (snappy_records.hip): records of 0 .. SNAPPY_BLOCK bytes at
+// (offset, length) pairs.  A matched record of L bytes owns records_need_words(L)
+// u32 words of scratch at its scanned offset: L / 4 + 2 token words, as many
+// escape words, then one (output offset, input position) pair per K2 segment.
+__host__ __device__ constexpr uint32_t records_tok_cap(uint32_t L) { return L / 4 + 2; }
+__host__ __device__ constexpr uint32_t records_segs(uint32_t L)
+{
+    return (records_tok_cap(L) + SNAPPY_K2_SEG - 1) / SNAPPY_K2_SEG;
+}
+__host__ __device__ constexpr uint32_t records_need_words(uint32_t L)
+{
+    return 2 * records_tok_cap(L) + 2 * records_segs(L);  // (even: the segment pairs stay 8-byte aligned)
+}
+// K1r / K1r64 over one class of a batch: workgroup b matches record list[b]
+__global__ void kr1_match_records(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                  const uint32_t *__restrict__ list, const uint64_t *__restrict__ sbase,
+                                  uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                  uint32_t *__restrict__ sizes);
+__global__ void kr1_match_records64(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                    const uint32_t *__restrict__ list, const uint64_t *__restrict__ sbase,
+                                    uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                    uint32_t *__restrict__ sizes);
+// K2 over every record (grid x = records, y = waves per record); status = the plan's words
+__global__ void kr2_emit_records(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                 const int32_t *__restrict__ status, const uint64_t *__restrict__ sbase,
+                                 const uint32_t *__restrict__ scratch, const uint32_t *__restrict__ ntok,
+                                 const uint64_t *__restrict__ offsets, uint8_t *__restrict__ out);
+// K4 pass 1, one wave per record; *first (~0 before) = min over failing records of record << 8 | -status
+__global__ void kr4_decode_records(const uint8_t *__restrict__ comp, uint32_t bias, uint64_t comp_bytes,
+                                   const uint64_t *__restrict__ comp_off_len, uint8_t *__restrict__ out,
+                                   uint64_t out_bytes, const uint64_t *__restrict__ out_off_len,
+                                   int32_t *__restrict__ status, unsigned long long *__restrict__ first);
+
 #ifndef SNAPPY_K5_CHUNK
 #define SNAPPY_K5_CHUNK 16384
 #endif

@@ -11,6 +11,10 @@
 //   K4  k4_decompress_*    tag-dispatch decode, block-parallel
 //                          (src/snappy_decompression.c:290-363)
 //   K5  k5_* / k5a-d       block index of a foreign single stream (K5a, K5b1-3, K5c, K5d)
+//   KR  kr1_match_records(64), kr2_emit_records, kr4_decode_records: the K1r, K2
+//                          and K4 pass 1 bodies over a record batch -- each unit's
+//                          place comes from tables, not from u * unit
+//                          (snappy_records.hip holds the plan pass and the launches)
 //
 // The hash table holds block-relative positions; 0 is a valid candidate,
 // exactly as in the reference (snappy_compression.c:259-265).
@@ -400,12 +404,25 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, ui
 // GiB, 32 KiB streams at matched loop placement 12.56 -> 12.34-12.36;
 // profiles/r05za_*, r05zs_*)
 
-template <bool BIG>
+// Where a unit's data live.  The fixed layouts (REC = false) compute it from the
+// unit's number: unit u is in[u * unit ..), its tokens at u * tok_cap, its
+// segment records at u * segs.  A record batch (REC = true, snappy_records.hip)
+// hands the body one record's places in a K1Record the entry point filled from
+// the plan pass's tables -- every field wave-uniform (the asm statements take
+// the source and the token and segment bases as "s" operands).
+struct K1Record {
+    uint32_t u;         // the record's number: ntok_out[u], sizes[u]
+    uint32_t L;         // its length, 1 .. 65,536
+    const uint8_t *src;
+    uint32_t *tok, *tok_full, *segu;  // L / 4 + 2 words each; ceil((L / 4 + 2) / kK2Seg) segment records
+};
+
+template <bool BIG, bool REC = false>
 __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit,
                                          uint32_t hdr_mode, uint64_t header_value,
                                          uint2 *__restrict__ tokens, uint32_t tok_cap,
                                          uint32_t *__restrict__ ntok_out, uint32_t *__restrict__ sizes,
-                                         uint32_t *__restrict__ seg_off, uint32_t segs)
+                                         uint32_t *__restrict__ seg_off, uint32_t segs, const K1Record rec = {})
 {
     constexpr int W = SNAPPY_K1R_WINDOW;
     constexpr uint32_t DMAX = BIG ? SNAPPY_K1R_DMAX64 : SNAPPY_K1R_DMAX;
@@ -477,10 +494,10 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // tag bits 16..23 of an entry against those of a hash|tag word
 #define TAG_EQ(e, w) ((((e) ^ (w)) & 0xFF0000u) == 0)
     const uint32_t lane = threadIdx.x;
-    const uint32_t u = blockIdx.x;
-    const uint64_t base = (uint64_t)u * unit;
-    const uint32_t L = (uint32_t)((n - base) < unit ? (n - base) : unit);
-    const uint8_t *src = in + base;
+    const uint32_t u = REC ? rec.u : blockIdx.x;
+    const uint64_t base = REC ? 0 : (uint64_t)u * unit;
+    const uint32_t L = REC ? rec.L : (uint32_t)((n - base) < unit ? (n - base) : unit);
+    const uint8_t *src = REC ? rec.src : in + base;
 #ifdef SNAPPY_K1R_STATS
     const uint64_t t_start = clock64();
     (void)t_start;
@@ -597,8 +614,9 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     // literal bytes before the copy; a length or gap that does not fit 8 bits
     // (255 = escape) puts gap | length << 16 in the same slot of a second array
     // (after all units' words), written only for those tokens
-    uint32_t *tok = reinterpret_cast<uint32_t *>(tokens) + (uint64_t)u * tok_cap;
-    uint32_t *tok_full = reinterpret_cast<uint32_t *>(tokens) + ((uint64_t)gridDim.x + u) * tok_cap;
+    uint32_t *tok = REC ? rec.tok : reinterpret_cast<uint32_t *>(tokens) + (uint64_t)u * tok_cap;
+    uint32_t *tok_full =
+        REC ? rec.tok_full : reinterpret_cast<uint32_t *>(tokens) + ((uint64_t)gridDim.x + u) * tok_cap;
     uint32_t tka = 0, tkb = 0;  // pending tokens: lane t < pend holds token nt + t
     uint32_t nt = 0, pend = 0;
     // encoded size so far (header, literals, copies: src/snappy_compression.c:95-165)
@@ -608,7 +626,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && u == 0) acc = varint_len(header_value);
     // K2 segment k (tokens kK2Seg k ..): its output offset in the unit and the
     // input position where its first token's literal starts
-    uint32_t *const segu = seg_off + 2 * (uint64_t)u * segs;
+    uint32_t *const segu = REC ? rec.segu : seg_off + 2 * (uint64_t)u * segs;
     auto flush_tokens = [&]() {
         const bool has = lane < pend;
         const uint32_t pos = tka & 0xFFFF, len = tka >> 16, end = pos + len;
@@ -1717,7 +1735,7 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
         sizes[u] = acc + (L > cend ? literal_bytes(L - cend) : 0u);
     }
 #ifdef SNAPPY_K1R_RSTAMPS
-    if (lane == 0) {
+    if (!REC && lane == 0) {
         uint64_t *st = reinterpret_cast<uint64_t *>(tokens + (uint64_t)gridDim.x * tok_cap) + 4 * (uint64_t)u;
         // (a unit's loop cycles < 2^30, its flush and window cycles < 2^24, glue cycles < 2^22)
         st[0] = (clock64() - t_loop) | (rs_gout << 30) | ((uint64_t)rs_ng << 52);
@@ -1729,7 +1747,7 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
     }
 #endif
 #ifdef SNAPPY_K1R_STATS
-    if (lane == 0) {
+    if (!REC && lane == 0) {
         uint64_t *st = reinterpret_cast<uint64_t *>(tokens + (uint64_t)gridDim.x * tok_cap) + 4 * (uint64_t)u;
         st[0] = clock64() - t_loop;
 #if defined(SNAPPY_K1R_LSTAMPS)
@@ -1768,6 +1786,58 @@ __global__ __launch_bounds__(64, 3) void k1r_match_units64(const uint8_t *__rest
                                                             uint32_t *__restrict__ seg_off, uint32_t segs)
 {
     k1r_body<true>(in, n, unit, hdr_mode, header_value, tokens, tok_cap, ntok_out, sizes, seg_off, segs);
+}
+#endif
+
+// Record batches (snappy_records.hip): workgroup b of a class's launch takes
+// record list[b].  Its source is in + off_len[2 r], its length off_len[2 r + 1]
+// (the plan pass let only 1 .. 32,768 into K1r's list and 32,769 .. 65,536 into
+// K1r64's), its scratch the records_need_words(L) words at scratch + sbase[r]:
+// tokens, escapes, segment records.  Everything is read through blockIdx.x and
+// made scalar before the body sees it.
+__device__ __forceinline__ uint64_t rfl64(uint64_t v)
+{
+    return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v);
+}
+
+template <bool BIG>
+__device__ __forceinline__ void kr1_record(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                           const uint32_t *__restrict__ list, const uint64_t *__restrict__ sbase,
+                                           uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                           uint32_t *__restrict__ sizes)
+{
+    K1Record rec;
+    rec.u = rfl(list[blockIdx.x]);
+    rec.L = rfl((uint32_t)off_len[2 * (uint64_t)rec.u + 1]);
+    rec.src = in + rfl64(off_len[2 * (uint64_t)rec.u]);
+    const uint32_t tok_cap = records_tok_cap(rec.L);
+    rec.tok = scratch + rfl64(sbase[rec.u]);
+    rec.tok_full = rec.tok + tok_cap;
+    rec.segu = rec.tok_full + tok_cap;
+    k1r_body<BIG, true>(nullptr, 0, 0, SNAPPY_HDR_EVERY_UNIT, 0, nullptr, 0, ntok_out, sizes, nullptr, 0, rec);
+}
+
+#if SNAPPY_TU_COMPRESS
+__global__ __launch_bounds__(64, 3) void kr1_match_records(const uint8_t *__restrict__ in,
+                                                            const uint64_t *__restrict__ off_len,
+                                                            const uint32_t *__restrict__ list,
+                                                            const uint64_t *__restrict__ sbase,
+                                                            uint32_t *__restrict__ scratch,
+                                                            uint32_t *__restrict__ ntok_out,
+                                                            uint32_t *__restrict__ sizes)
+{
+    kr1_record<false>(in, off_len, list, sbase, scratch, ntok_out, sizes);
+}
+
+__global__ __launch_bounds__(64, 3) void kr1_match_records64(const uint8_t *__restrict__ in,
+                                                              const uint64_t *__restrict__ off_len,
+                                                              const uint32_t *__restrict__ list,
+                                                              const uint64_t *__restrict__ sbase,
+                                                              uint32_t *__restrict__ scratch,
+                                                              uint32_t *__restrict__ ntok_out,
+                                                              uint32_t *__restrict__ sizes)
+{
+    kr1_record<true>(in, off_len, list, sbase, scratch, ntok_out, sizes);
 }
 #endif
 
@@ -1988,6 +2058,12 @@ __device__ __forceinline__ void k2_long_literals(uint8_t *w, const uint8_t *__re
 #ifndef SNAPPY_K2_NOLIT
 #define SNAPPY_K2_NOLIT 0
 #endif
+// One record's places for a record batch (kr2_emit_records; see K1Record)
+struct K2Record {
+    uint32_t L;
+    const uint32_t *tok, *tok_full, *segu;
+};
+
 #if SNAPPY_TU_COMPRESS
 __global__ __launch_bounds__(64, 6) void k2_emit_units(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit,
                                                     uint32_t hdr_mode, uint64_t header_value,
@@ -1996,146 +2072,51 @@ __global__ __launch_bounds__(64, 6) void k2_emit_units(const uint8_t *__restrict
                                                     const uint32_t *__restrict__ seg_off, uint32_t segs,
                                                     const uint64_t *__restrict__ offsets, uint8_t *__restrict__ out)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage_[kK2Stage + 4 + 4 * 64 + 16];  // + alignment, per-lane dummies
-    auto *const stage = (__attribute__((address_space(3))) uint8_t *)stage_;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t u = blockIdx.x;
-    const uint32_t nt = ntok[u];
-    const uint64_t base = (uint64_t)u * unit;
-    const uint32_t L = (uint32_t)((n - base) < unit ? (n - base) : unit);
-    const uint8_t *src = in + base;
-    uint8_t *dst = out + offsets[u];
-    // 4-byte tokens (K1r: offset | (length - 4) << 16 | gap << 24, escapes in tok_full)
-    const uint32_t *tok = reinterpret_cast<const uint32_t *>(tokens) + (uint64_t)u * tok_cap;
-    const uint32_t *tok_full = reinterpret_cast<const uint32_t *>(tokens) + ((uint64_t)gridDim.x + u) * tok_cap;
-    if (blockIdx.y == 0) {
-        if (hdr_mode == SNAPPY_HDR_EVERY_UNIT) varint_put(L, dst, lane);
-        else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && u == 0) varint_put(header_value, dst, lane);
-    }
-    // the next pass's token words (and the next segment's record) are loaded one
-    // pass ahead, so their round trip overlaps this pass's literal loads
-    uint32_t kwn[kK2Per];
-    auto load_kw = [&](uint32_t c, uint32_t *k) {
-#pragma unroll
-        for (uint32_t i = 0; i < kK2Per; i++) {
-            const uint32_t t = c + kK2Per * lane + i;
-            k[i] = tok[t < nt ? t : 0u];
-        }
-    };
-    auto load_se = [&](uint32_t sg) {
-        return *reinterpret_cast<const uint2 *>(seg_off + 2 * ((uint64_t)u * segs + (sg * kK2Seg <= nt ? sg : 0u)));
-    };
-    if (blockIdx.y * kK2Seg <= nt) load_kw(blockIdx.y * kK2Seg, kwn);
-    uint2 sen = load_se(blockIdx.y);
-    for (uint32_t sg = blockIdx.y; sg * kK2Seg <= nt; sg += gridDim.y) {
-    // K1r's table: the segment's output offset and the input position where
-    // its first literal starts (the end of the previous segment's last token)
-    const uint2 se = sen;
-    sen = load_se(sg + gridDim.y);
-    uint32_t o = se.x, carry = se.y;
-    for (uint32_t c = sg * kK2Seg; c < (sg + 1) * kK2Seg && c <= nt; c += kK2Pass) {
+#define K2_RECORDS 0
+#include "snappy_k2_emit.inc"
+#undef K2_RECORDS
+}
 
-    uint32_t gap[kK2Per], len[kK2Per], off[kK2Per], pe[kK2Per], litn[kK2Per], hl[kK2Per], sz[kK2Per];
-    bool live[kK2Per];
-    uint32_t lspan = 0;  // input bytes covered by the lane's tokens (literal + copy)
-    // the lane's token words in one round trip (a lane past the end re-reads word 0:
-    // no branch, so no load waits for the one before it), then the rare escapes
-    uint32_t kw[kK2Per];
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) kw[i] = kwn[i];
-    {
-        uint32_t cn = c + kK2Pass;
-        if (!(cn < (sg + 1) * kK2Seg && cn <= nt)) cn = (sg + gridDim.y) * kK2Seg;
-        if (cn <= nt) load_kw(cn, kwn);
+// K2's body over one record (`in`, `n`: the record's own start and length)
+__device__ __forceinline__ void kr2_emit_one(const uint8_t *in, const K2Record rec, const uint32_t *ntok,
+                                             const uint64_t *offsets, uint8_t *out)
+{
+    const uint64_t n = rec.L, header_value = 0;
+    const uint32_t hdr_mode = SNAPPY_HDR_EVERY_UNIT;
+#define K2_RECORDS 1
+#include "snappy_k2_emit.inc"
+#undef K2_RECORDS
+}
+
+// Record batches: workgroup x is record x (every record: K3 gave each its place
+// in out), y the wave of its segments.  status[x] is the plan pass's word: a
+// refused record (< 0) writes nothing, an empty one its one byte 00, neither
+// touches the input; the others were matched by kr1_match_records(64).
+__global__ __launch_bounds__(64, 6) void kr2_emit_records(const uint8_t *__restrict__ base,
+                                                          const uint64_t *__restrict__ off_len,
+                                                          const int32_t *__restrict__ status,
+                                                          const uint64_t *__restrict__ sbase,
+                                                          const uint32_t *__restrict__ scratch,
+                                                          const uint32_t *__restrict__ ntok,
+                                                          const uint64_t *__restrict__ offsets,
+                                                          uint8_t *__restrict__ out)
+{
+    const uint32_t r = blockIdx.x;
+    // (the record's four table words in one round trip, before the first test)
+    const int32_t st = status[r];
+    const uint64_t off = off_len[2 * (uint64_t)r], len = off_len[2 * (uint64_t)r + 1], sb = sbase[r];
+    if (st < 0) return;
+    K2Record rec;
+    rec.L = rfl((uint32_t)len);
+    if (rec.L == 0) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) out[offsets[r]] = 0;
+        return;
     }
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) {
-        const uint32_t t = c + kK2Per * lane + i;
-        const bool has = t < nt;  // else the pseudo-token (the tail literal) or nothing
-        live[i] = t <= nt;
-        const uint32_t k = has ? kw[i] : 0xFFFFFFFFu;
-        const uint32_t lc = (k >> 16) & 0xFF, gc = k >> 24;
-        off[i] = has ? k & 0xFFFF : 0u;
-        gap[i] = has ? gc : 0u;
-        len[i] = has ? lc + 4 : 0u;
-        if (has && (lc == 255 || gc == 255)) {
-            const uint32_t f = tok_full[t];
-            gap[i] = f & 0xFFFF;
-            len[i] = f >> 16;
-        }
-        lspan += gap[i] + len[i];
-    }
-    uint32_t span_tot;
-    uint32_t cur = carry + wave_excl_scan(lspan, lane, &span_tot);
-    uint32_t lsum = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) {
-        const uint32_t t = c + kK2Per * lane + i;
-        pe[i] = cur;  // where the token's literal starts
-        litn[i] = t < nt ? gap[i] : (t == nt ? L - cur : 0u);
-        cur += gap[i] + len[i];
-        hl[i] = litn[i] ? (litn[i] <= 60 ? 1 : (litn[i] <= 256 ? 2 : 3)) : 0;
-        sz[i] = hl[i] + litn[i] + ((live[i] && len[i]) ? copy_bytes(len[i], off[i]) : 0);
-        lsum += sz[i];
-    }
-    uint32_t total;
-    uint32_t rel = wave_excl_scan(lsum, lane, &total);
-    const bool staged = total <= kK2Stage;
-    // the stage is laid out at the destination's alignment (stage byte sb + x is
-    // output byte dst + o + x), so the copy-out below reads aligned LDS dwords
-    const uint32_t sb = staged ? (uint32_t)(reinterpret_cast<uintptr_t>(dst + o) & 3) : 0u;
-    uint64_t longs[kK2Per];
-    uint32_t d0v[kK2Per];
-    // every short literal's source dwords in one round trip: lanes with none read
-    // the unit's first token words (in bounds, ignored)
-    uint32_t lw[kK2Per][5], lsh[kK2Per];
-    bool wide[kK2Per];
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) {
-        wide[i] = base + pe[i] + 20 <= n;  // the aligned 20-byte read ends inside in[0, n)
-        const bool ld = !SNAPPY_K2_NOLIT && staged && wide[i] && live[i] && litn[i] != 0 && litn[i] <= 16;
-        const uintptr_t sa = reinterpret_cast<uintptr_t>(src + pe[i]);
-        lsh[i] = (uint32_t)(sa & 3);
-        const auto *aw = reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(
-            ld ? sa - lsh[i] : reinterpret_cast<uintptr_t>(tok));
-#pragma unroll
-        for (uint32_t j = 0; j < 5; j++) lw[i][j] = aw[j];
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per; i++) {
-        const bool wide_ok = wide[i];
-        if (staged) put_element_lds(stage, rel + sb, src, pe[i], litn[i], hl[i], len[i], off[i], wide_ok, live[i], lane,
-                                    lw[i], lsh[i]);
-        else if (live[i]) put_element(dst + o + rel, src, pe[i], litn[i], hl[i], len[i], off[i], wide_ok);
-        longs[i] = __ballot(live[i] && litn[i] > 16);
-        d0v[i] = rel + sb + hl[i];
-        rel += sz[i];
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kK2Per && !SNAPPY_K2_NOLIT; i++) {
-        if (staged) k2_long_literals(stage, src, longs[i], litn[i], pe[i], d0v[i], lane);
-        else k2_long_literals(dst + o, src, in + n, longs[i], litn[i], pe[i], d0v[i], lane);
-    }
-    if (staged) {
-        __builtin_amdgcn_wave_barrier();
-        // stage[sb, sb + total) -> dst + o: byte head to a dword boundary, aligned
-        // dwords (aligned in LDS too: sb + head is a multiple of 4), byte tail
-        uint8_t *g = dst + o;
-        uint32_t head = (4 - sb) & 3;
-        if (head > total) head = total;
-        if (lane < head) g[lane] = stage[sb + lane];
-        const uint32_t nw = (total - head) >> 2;
-        uint32_t *gw = reinterpret_cast<uint32_t *>(g + head);
-        const auto *sw = reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>(stage + sb + head);
-        for (uint32_t k = lane; k < nw; k += 64) gw[k] = sw[k];
-        const uint32_t tail0 = head + 4 * nw;
-        if (lane < total - tail0) g[tail0 + lane] = stage[sb + tail0 + lane];
-    }
-    __builtin_amdgcn_wave_barrier();  // the stage is reused by the next pass
-    o += total;
-    carry += span_tot;
-    }
-    }
+    const uint32_t tok_cap = records_tok_cap(rec.L);
+    rec.tok = scratch + rfl64(sb);
+    rec.tok_full = rec.tok + tok_cap;
+    rec.segu = rec.tok_full + tok_cap;
+    kr2_emit_one(base + rfl64(off), rec, ntok, offsets, out);
 }
 #endif
 
@@ -2431,12 +2412,25 @@ constexpr uint32_t kK4RingAt = kK4TailAt + 16;
 #endif
 constexpr uint32_t kK4Lds = kK4RingAt + kK4Ring + 4 + SNAPPY_K4_LDS_PAD;  // 5,028 B: 32 waves per CU fit 160 KiB
 
-template <bool BACK>
+// One record of a record batch (REC = true, pass 1 only): the entry point
+// checked its ranges and hands over where its compressed bytes are (c0, from
+// the 4-aligned comp, clen bytes: the record's own end bounds every read), where
+// its output goes (out + out_off, `want` bytes) and the status it starts with
+// (not OK: the record fails with it, and nothing of it is loaded or stored).
+struct K4Record {
+    uint64_t c0, clen, out_off;
+    uint32_t want;
+    int32_t st;
+    unsigned long long *first;  // the batch's first failure: min over (record << 8 | -status)
+};
+
+template <bool BACK, bool REC = false>
 __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const uint64_t *__restrict__ offsets,
                                         uint64_t n, uint32_t unit, uint32_t hdr_mode, uint64_t header_value,
                                         uint32_t allow_back, uint32_t bias, uint8_t *__restrict__ out,
-                                        int32_t *__restrict__ status, uint32_t u)
+                                        int32_t *__restrict__ status, uint32_t u, const K4Record rec = {})
 {
+    static_assert(!(BACK && REC), "records are their own streams: there is no second pass");
     // copy source positions: relative to the unit start, negative = an earlier unit (pass 2 only)
     using SrcT = typename std::conditional<BACK, int64_t, uint32_t>::type;
     __shared__ __attribute__((aligned(16))) uint32_t lds[kK4Lds / 4];
@@ -2444,18 +2438,19 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
     constexpr uint32_t ring = kK4Ring, M = ring - 1;
     uint32_t *const map32 = lds + kK4MapAt / 4;      // the batch's element starts, 32 dwords
     const uint32_t lane = threadIdx.x;
-    const uint64_t ix0 = offsets[u], ix1 = offsets[u + 1];
+    const uint64_t ix0 = REC ? 0 : offsets[u], ix1 = REC ? 0 : offsets[u + 1];
     // comp is 4-byte aligned; the stream starts `bias` bytes into it
-    const uint64_t c0 = (ix0 & kIdxOffMask) + bias, c1n = (ix1 & kIdxOffMask) + bias;
+    const uint64_t c0 = REC ? rec.c0 : (ix0 & kIdxOffMask) + bias;
+    const uint64_t c1n = REC ? rec.c0 + rec.clen : (ix1 & kIdxOffMask) + bias;
     const uint32_t skip0 = (uint32_t)(ix0 >> kIdxSkipShift), skip1 = (uint32_t)(ix1 >> kIdxSkipShift);
-    const uint64_t base = (uint64_t)u * unit;
-    const uint32_t want = (uint32_t)((n - base) < unit ? (n - base) : unit);
-    int32_t st = SNAPPY_ST_OK;
+    const uint64_t base = REC ? rec.out_off : (uint64_t)u * unit;
+    const uint32_t want = REC ? rec.want : (uint32_t)((n - base) < unit ? (n - base) : unit);
+    int32_t st = REC ? rec.st : SNAPPY_ST_OK;
     // the unit's compressed bytes: up to the next entry, or (its last element
     // straddling out) as far as the stream goes
     // (the last entry is the stream end: no read goes past it, whatever the
     // entries in between say -- a corrupt index fails as TRUNCATED, not a fault)
-    const uint64_t c_end = (offsets[(n + unit - 1) / unit] & kIdxOffMask) + bias;
+    const uint64_t c_end = REC ? c1n : (offsets[(n + unit - 1) / unit] & kIdxOffMask) + bias;
     uint64_t c1 = skip1 ? c_end : c1n;
     if (c1 > c_end) c1 = c_end;
     if (c1 > c0 + 0x7FFFFFFFull) c1 = c0 + 0x7FFFFFFFull;
@@ -3114,6 +3109,13 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
     k4_flush(ob, M, dst, F, op < want ? op : want, lane);
     if constexpr (BACK) {
         k4_publish(status, u, st, lane);
+    } else if constexpr (REC) {
+        // a copy reaching before the record's start (DEFER: there is no pass 2) is the record's error
+        if (st == SNAPPY_ST_DEFER) st = SNAPPY_ST_OFFSET;
+        if (lane == 0) {
+            status[u] = st;
+            if (st != SNAPPY_ST_OK) atomicMin(rec.first, ((unsigned long long)u << 8) | (uint32_t)-st);
+        }
     } else {
         if (lane == 0) status[u] = st;
         // status[units + 1] = pass 2 has work (status[units] is pass 2's ticket counter)
@@ -3131,6 +3133,35 @@ __global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void k4_decompress_units(
     int32_t *__restrict__ status)
 {
     k4_body<false>(comp, offsets, n, unit, hdr_mode, header_value, allow_back, bias, out, status, blockIdx.x);
+}
+
+// Record batches: one wave per record, each its own stream (the preamble check
+// of SNAPPY_HDR_EVERY_UNIT, no copies before the record's start).  comp is
+// 4-byte aligned, the records' offsets count from comp + bias.  The range
+// checks come first, so a record that fails them ends before its first load:
+//   out_len > 65,536 UNSUPPORTED; compressed range outside comp_bytes TRUNCATED;
+//   output range outside out_bytes CAPACITY; an empty compressed range HEADER
+__global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_decode_records(
+    const uint8_t *__restrict__ comp, uint32_t bias, uint64_t comp_bytes, const uint64_t *__restrict__ comp_off_len,
+    uint8_t *__restrict__ out, uint64_t out_bytes, const uint64_t *__restrict__ out_off_len,
+    int32_t *__restrict__ status, unsigned long long *__restrict__ first)
+{
+    const uint32_t r = blockIdx.x;
+    const uint64_t co = rfl64(comp_off_len[2 * (uint64_t)r]), cl = rfl64(comp_off_len[2 * (uint64_t)r + 1]);
+    const uint64_t oo = rfl64(out_off_len[2 * (uint64_t)r]), ol = rfl64(out_off_len[2 * (uint64_t)r + 1]);
+    K4Record rec;
+    rec.st = SNAPPY_ST_OK;
+    if (ol > SNAPPY_BLOCK) rec.st = SNAPPY_ST_UNSUPPORTED;
+    else if (co > comp_bytes || cl > comp_bytes - co) rec.st = SNAPPY_ST_TRUNCATED;
+    else if (oo > out_bytes || ol > out_bytes - oo) rec.st = SNAPPY_ST_CAPACITY;
+    else if (cl == 0) rec.st = SNAPPY_ST_HEADER;
+    const bool ok = rec.st == SNAPPY_ST_OK;
+    rec.c0 = ok ? co + bias : 0;
+    rec.clen = ok ? cl : 0;
+    rec.out_off = ok ? oo : 0;
+    rec.want = ok ? (uint32_t)ol : 0u;
+    rec.first = first;
+    k4_body<false, true>(comp, nullptr, 0, 0, SNAPPY_HDR_EVERY_UNIT, 0, 0u, bias, out, status, r, rec);
 }
 #endif
 

@@ -41,6 +41,7 @@ FRAME_IDENTIFIER = bytes.fromhex("ff060000734e61507059")
 IDX_MAGIC = 0x3158444941504E53  # b"SNPAIDX1" as a little-endian u64
 
 BLOCK = 65536
+RECORD_MAX = 65536  # decoded bytes of one record of a record batch
 SINGLE = 0
 STREAMS = 1
 NO_PREAMBLE = 1
@@ -143,6 +144,17 @@ _SIGS = {
     "snappy_decompress_frame_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
                                                   _c.POINTER(_c.c_size_t)]),
     "snappy_frame_uncompressed_length": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint64)]),
+    # record batches
+    "snappy_amd_max_records_output": (_c.c_size_t, [_c.c_size_t, _c.c_size_t]),
+    "snappy_amd_max_records_scratch": (_c.c_size_t, [_c.c_size_t, _c.c_size_t]),
+    "snappy_amd_compress_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                      _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p,
+                                                      _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_records_length_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                    _c.c_void_p, _c.c_void_p]),
+    "snappy_amd_decompress_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                        _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                        _c.c_void_p, _c.c_int]),
     "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
     "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
 }
@@ -341,6 +353,16 @@ def decompress_frame(data, cap: Optional[int] = None) -> bytes:
     got = ctypes.c_size_t(0)
     _check(lib().snappy_decompress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "decompress_frame")
     return out.raw[: got.value]
+
+
+def max_records_output(total_bytes: int, count: int) -> int:
+    """Capacity the output of a compress_records call must have."""
+    return lib().snappy_amd_max_records_output(total_bytes, count)
+
+
+def max_records_scratch(total_bytes: int, count: int) -> int:
+    """Upper bound of Codec.device_bytes() after a compress_records call."""
+    return lib().snappy_amd_max_records_scratch(total_bytes, count)
 
 
 def read_index(data: bytes):
@@ -579,3 +601,133 @@ class Codec:
                                                         ctypes.c_void_p(out.data_ptr()), n, ctypes.byref(got)),
                "decompress_frame_device")
         return out[: got.value]
+
+    # record batches ------------------------------------------------------------
+    def compress_records_tensor(self, base, off_len, out=None, want_status: bool = True, check: bool = False):
+        """Compress the records of `base` (uint8 CUDA tensor) that off_len names
+        (int64 CUDA tensor of (offset, length) pairs, lengths 0..65,536) ->
+        (payload tensor, offsets tensor of count + 1, status tensor of count).
+        A refused record has size 0 and its code in the status tensor; check=True
+        raises SnappyError with the first refusal instead."""
+        assert base.is_cuda and base.dtype == torch.uint8 and base.is_contiguous()
+        assert off_len.is_cuda and off_len.dtype == torch.int64 and off_len.is_contiguous()
+        count = off_len.numel() // 2
+        if out is None:
+            # (an upper bound of the accepted bytes without a read-back: each record min(length, 65,536))
+            total = int(off_len.view(-1, 2)[:, 1].clamp(0, RECORD_MAX).sum().item()) if count else 0
+            out = torch.empty(max_records_output(total, count), dtype=torch.uint8, device=base.device)
+        offs = torch.empty(count + 1, dtype=torch.int64, device=base.device)
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=base.device) if want_status else None
+        got = ctypes.c_size_t(0)
+        self._bind_stream()
+        rc = lib().snappy_amd_compress_records_device(
+            self._h, ctypes.c_void_p(base.data_ptr()), base.numel(), ctypes.c_void_p(off_len.data_ptr()), count,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(offs.data_ptr()),
+            ctypes.c_void_p(status.data_ptr()) if want_status else None, ctypes.byref(got))
+        self.last_records_status = rc
+        # a refusal is reported per record; anything else (capacity, device, arguments) failed the call
+        if rc != OK and (check or rc not in (ERR_UNSUPPORTED, ERR_ARG) or count == 0):
+            raise SnappyError(rc, "compress_records_device")
+        return out[: got.value], offs, (status[:count] if want_status else None)
+
+    def records_length_tensor(self, comp, off_len):
+        """The declared length of every record -> (int64 lengths, int32 status)."""
+        assert comp.is_cuda and comp.dtype == torch.uint8 and off_len.is_cuda and off_len.dtype == torch.int64
+        count = off_len.numel() // 2
+        lens = torch.zeros(max(count, 1), dtype=torch.int64, device=comp.device)
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=comp.device)
+        self._bind_stream()
+        _check(lib().snappy_amd_records_length_device(self._h, ctypes.c_void_p(comp.data_ptr()), comp.numel(),
+                                                      ctypes.c_void_p(off_len.data_ptr()), count,
+                                                      ctypes.c_void_p(lens.data_ptr()),
+                                                      ctypes.c_void_p(status.data_ptr())), "records_length_device")
+        return lens[:count], status[:count]
+
+    def decompress_records_tensor(self, comp, comp_off_len, out, out_off_len, want_status: bool = True,
+                                  check: bool = False):
+        """Decode record i of `comp` (comp_off_len pairs) into `out` at out_off_len[i]
+        (both int64 CUDA tensors of (offset, length) pairs) -> int32 status tensor.
+        check=True raises SnappyError with the first failing record's code."""
+        assert comp.is_cuda and comp.dtype == torch.uint8 and out.is_cuda and out.dtype == torch.uint8
+        assert comp_off_len.dtype == torch.int64 and out_off_len.dtype == torch.int64
+        assert comp_off_len.numel() == out_off_len.numel()
+        count = comp_off_len.numel() // 2
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=comp.device) if want_status else None
+        self._bind_stream()
+        rc = lib().snappy_amd_decompress_records_device(
+            self._h, ctypes.c_void_p(comp.data_ptr()), comp.numel(), ctypes.c_void_p(comp_off_len.data_ptr()), count,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(out_off_len.data_ptr()),
+            ctypes.c_void_p(status.data_ptr()) if want_status else None, 1)
+        self.last_records_status = rc
+        if rc != OK and (check or rc in (ERR_DEVICE, ERR_ARG)):
+            raise SnappyError(rc, "decompress_records_device")
+        return status[:count] if want_status else None
+
+    @staticmethod
+    def _upload(data: bytes, dev):
+        import numpy as np
+        if not data:
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        return torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev)
+
+    def compress_records(self, records) -> list:
+        """list of bytes-like records (each 0..65,536 bytes) -> list of their raw
+        Snappy streams: packed, uploaded, compressed in one call."""
+        import numpy as np
+        records = [bytes(r) for r in records]
+        if not records:
+            return []
+        lens = np.array([len(r) for r in records], dtype=np.int64)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        dev = torch.device("cuda", self.device)
+        base = self._upload(b"".join(records), dev)
+        off_len = torch.from_numpy(np.stack([offs, lens], axis=1).reshape(-1).copy()).to(dev)
+        payload, o, _ = self.compress_records_tensor(base, off_len, check=True)
+        o, p = o.cpu().numpy(), payload.cpu().numpy().tobytes()
+        return [p[int(o[i]): int(o[i + 1])] for i in range(len(records))]
+
+    def decompress_records(self, records) -> list:
+        """list of raw Snappy streams -> list of their decoded bytes: one length
+        call and one decode call; raises SnappyError with the first failing
+        record's code."""
+        import numpy as np
+        records = [bytes(r) for r in records]
+        if not records:
+            return []
+        clens = np.array([len(r) for r in records], dtype=np.int64)
+        coffs = np.concatenate(([0], np.cumsum(clens)[:-1])).astype(np.int64)
+        dev = torch.device("cuda", self.device)
+        comp = self._upload(b"".join(records), dev)
+        c_ol = torch.from_numpy(np.stack([coffs, clens], axis=1).reshape(-1).copy()).to(dev)
+        lens, st = self.records_length_tensor(comp, c_ol)
+        lens, st = lens.cpu().numpy(), st.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            raise SnappyError(int(st[bad[0]]), f"decompress_records: record {int(bad[0])}")
+        big = np.nonzero(lens > RECORD_MAX)[0]
+        if big.size:
+            raise SnappyError(ERR_UNSUPPORTED, f"decompress_records: record {int(big[0])}")
+        ooffs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        out = torch.empty(max(int(lens.sum()), 1), dtype=torch.uint8, device=dev)[: int(lens.sum())]
+        o_ol = torch.from_numpy(np.stack([ooffs, lens], axis=1).reshape(-1).copy()).to(dev)
+        self.decompress_records_tensor(comp, c_ol, out, o_ol, want_status=False, check=True)
+        flat = out.cpu().numpy().tobytes()
+        return [flat[int(ooffs[i]): int(ooffs[i] + lens[i])] for i in range(len(records))]
+
+
+def compress_records(records, device: int = 0) -> list:
+    """Codec(device).compress_records(records) on a context of its own."""
+    c = Codec(device)
+    try:
+        return c.compress_records(records)
+    finally:
+        c.close()
+
+
+def decompress_records(records, device: int = 0) -> list:
+    """Codec(device).decompress_records(records) on a context of its own."""
+    c = Codec(device)
+    try:
+        return c.decompress_records(records)
+    finally:
+        c.close()

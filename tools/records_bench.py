@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Record-batch timings on one GPU (the protocol of tools/frame_bench.py): N
+bytes of datagen text in HBM, HIP events on the codec's stream, medians of
+`reps` repetitions after two warm-up rounds, all calls alternating in the same
+process.  Compress and decode each:
+
+  a  uniform 32,768-byte records   vs  the STREAMS call, chunk 32,768
+  b  uniform 65,536-byte records   vs  the STREAMS call, chunk 65,536
+  c  a seeded log-uniform mix of 64 B .. 64 KiB records, N bytes in all
+  d  4 KiB records
+
+The STREAMS calls are the yardstick of a and b (their min..max is the spread a
+difference has to exceed); c and d have no fixed-layout counterpart.
+
+Prints one JSON line and writes it to profiles/<tag>.json when a tag is given:
+    python tools/records_bench.py [n_bytes] [reps] [tag]
+Run under rocprofv3 --kernel-trace --stats (a run of its own) for per-kernel times."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lightweight-snappy_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import datagen  # noqa: E402
+import snappy_amd  # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 30
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 11
+tag = sys.argv[3] if len(sys.argv) > 3 else ""
+
+host = np.empty(n, dtype=np.uint8)
+datagen.fill(host, "T", 1234, threads=16)
+x = torch.from_numpy(host).cuda()
+del host
+codec = snappy_amd.Codec(0)
+stream = torch.cuda.Stream()
+codec.set_stream(stream.cuda_stream)
+lib, h, vp, ct = snappy_amd.lib(), codec._h, snappy_amd.ctypes.c_void_p, snappy_amd.ctypes
+
+
+def uniform(ln):
+    offs = np.arange(0, n, ln, dtype=np.int64)
+    return np.stack([offs, np.minimum(ln, n - offs)], axis=1)
+
+
+def log_uniform(seed=1234):
+    rng = np.random.default_rng(seed)
+    lens = np.exp(rng.uniform(np.log(64), np.log(65536), size=n // 64 + 1)).astype(np.int64)
+    ends = np.cumsum(lens)
+    k = int(np.searchsorted(ends, n)) + 1
+    lens = lens[:k]
+    lens[-1] -= ends[k - 1] - n  # the last record ends the buffer
+    return np.stack([np.concatenate(([0], ends[:k - 1])), lens], axis=1)
+
+
+legs = {"a": uniform(32768), "b": uniform(65536), "c": log_uniform(), "d": uniform(4096)}
+legs = {k: v[v[:, 1] > 0] for k, v in legs.items()}
+max_count = max(len(v) for v in legs.values())
+out = torch.empty(snappy_amd.max_records_output(n, max_count), dtype=torch.uint8, device="cuda")
+back = torch.empty(n, dtype=torch.uint8, device="cuda")
+dev = {}
+for k, v in legs.items():
+    dev[k] = {"ol": torch.from_numpy(v.reshape(-1).copy()).cuda(), "count": len(v),
+              "offs": torch.empty(len(v) + 1, dtype=torch.int64, device="cuda"),
+              "col": torch.empty(2 * len(v), dtype=torch.int64, device="cuda"), "clen": 0}
+state = {}
+
+
+def compress_records(k):
+    d = dev[k]
+    got = ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_compress_records_device(h, vp(x.data_ptr()), n, vp(d["ol"].data_ptr()), d["count"],
+                                                             vp(out.data_ptr()), out.numel(), vp(d["offs"].data_ptr()),
+                                                             None, ct.byref(got)), "compress_records_device")
+    d["clen"] = got.value
+
+
+def decode_records(k):
+    d = dev[k]
+    snappy_amd._check(lib.snappy_amd_decompress_records_device(h, vp(out.data_ptr()), d["clen"], vp(d["col"].data_ptr()),
+                                                               d["count"], vp(back.data_ptr()), n, vp(d["ol"].data_ptr()),
+                                                               None, 1), "decompress_records_device")
+
+
+def compress_streams(chunk):
+    state["plen"] = codec.compress_ptr(x.data_ptr(), n, chunk, snappy_amd.STREAMS, out.data_ptr(), state["soffs"].data_ptr())
+
+
+def decode_streams(chunk):
+    codec.decompress_ptr(out.data_ptr(), state["soffs"].data_ptr(), n, chunk, snappy_amd.STREAMS, back.data_ptr())
+
+
+def timed(fn, *args):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    fn(*args)
+    b.record(stream)
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+ms = {}
+with torch.cuda.stream(stream):
+    for r in range(reps + 2):  # two warm-up rounds (code objects, scratch growth)
+        for k in "abcd":
+            d = dev[k]
+            chunk = {"a": 32768, "b": 65536}.get(k)
+            t = {"compress_records": timed(compress_records, k)}
+            # the compressed records' (offset, length) pairs, on the device (not timed)
+            o = d["offs"]
+            d["col"].copy_(torch.stack([o[:-1], o[1:] - o[:-1]], dim=1).reshape(-1))
+            if r == 1:
+                state[k + "_payload"] = out[: d["clen"]].clone() if chunk else None
+            if r == 1:
+                back.zero_()
+            t["decode_records"] = timed(decode_records, k)
+            if r == 1:
+                assert torch.equal(back, x), f"leg {k}: record round trip failed"
+            if chunk:
+                state["soffs"] = torch.empty(d["count"] + 1, dtype=torch.int64, device="cuda")
+                t["compress_streams"] = timed(compress_streams, chunk)
+                if r == 1:
+                    assert state["plen"] == d["clen"] and torch.equal(out[: d["clen"]], state[k + "_payload"]), \
+                        f"leg {k}: records != STREAMS"
+                    assert torch.equal(state["soffs"], o)
+                    state[k + "_payload"] = None
+                t["decode_streams"] = timed(decode_streams, chunk)
+            if r >= 2:
+                for name, v in t.items():
+                    ms.setdefault(f"{k}_{name}", []).append(v)
+stream.synchronize()
+held = codec.device_bytes()
+codec.close()
+med = {k: median(v) for k, v in ms.items()}
+res = {"n": n, "reps": reps, "records": {k: dev[k]["count"] for k in "abcd"},
+       "compressed_bytes": {k: dev[k]["clen"] for k in "abcd"}, "device_bytes": held, "median_ms": med,
+       "a_compress_ratio": med["a_compress_records"] / med["a_compress_streams"],
+       "a_decode_ratio": med["a_decode_records"] / med["a_decode_streams"],
+       "b_compress_ratio": med["b_compress_records"] / med["b_compress_streams"],
+       "b_decode_ratio": med["b_decode_records"] / med["b_decode_streams"],
+       "min_max_ms": {k: [min(v), max(v)] for k, v in ms.items()}}
+line = json.dumps(res)
+print(line)
+if tag:
+    with open(os.path.join(ROOT, "profiles", tag + ".json"), "w") as f:
+        f.write(line + "\n")
