@@ -298,6 +298,98 @@ int snappy_amd_decompress_records_device(snappy_amd_ctx *ctx, const void *d_comp
                                          const uint64_t *d_comp_off_len, size_t count, void *d_out, size_t out_bytes,
                                          const uint64_t *d_out_off_len, int32_t *d_status, int sync);
 
+/* ---- long records: records of more than one block ------------------------- */
+/* The calls above refuse a record above 65,536 bytes.  These take records of
+ * 0..SNAPPY_AMD_LONG_RECORD_MAX decoded bytes -- a Parquet data page, an ORC
+ * compression chunk, a large RPC payload -- each one raw Snappy stream, exactly
+ * the bytes of snappy_compress(): varint(L), then blocks of 65,536 input bytes,
+ * the last one shorter.  Records of 0..65,536 bytes are legal here and give the
+ * bytes of the short calls.
+ *
+ * Block table (d_index, u64): record i has nblk_i = ceil(L_i / 65536) blocks and
+ * owns nblk_i + 1 entries; the tables are packed in record order, record i's at
+ * entry sum over k < i of (nblk_k + 1).  Entries have the format of
+ * snappy_amd_index_device (bits [0,40) an offset, bits [40,64) a skip), their
+ * offsets counted from the record's own first compressed byte: entry 0 is 0 (the
+ * preamble), entry nblk (nblk >= 1) the record's compressed length; an empty or
+ * a refused record owns the one entry 0.  Compress writes the tables; decode and
+ * records_index_device find each record's slice by the same rule from the
+ * decoded lengths, so a table holds only for the record order it was made for:
+ * a caller who reorders records passes NULL or rebuilds it.
+ * snappy_amd_max_records_index(total, count) = total/65536 + 2 count entries
+ * hold the tables of `count` records of `total` bytes.
+ *
+ * Scratch: a call grows snappy_amd_device_bytes() to at most
+ * snappy_amd_max_long_records_scratch(total, count) = S + S/8 + 24,704 with
+ *   S = 2 total + total/128 + 80 U + 64 count + 8 E + 512,
+ *   U = total/65536 + count (units: blocks, one per empty record),
+ *   E = total/65536 + 2 count (table entries).
+ * Per unit of L bytes: 8 (L/4 + 2) bytes of tokens and escapes and 8 bytes per
+ * 256 tokens of segment records (<= 2 L + L/128 + 28), 8 bytes of size and token
+ * count, 32 bytes of unit tables (record word, scratch need, two list slots,
+ * scratch offset, output offset) -- 68, counted as 80; the decode's 8 bytes per
+ * unit (record word, status word) reuse the unit tables' buffer.  Per record: 28
+ * bytes of plan tables and pass 2's two words, counted as 64.  8 bytes per
+ * table entry when decode builds the tables.  The eighth and the constant are
+ * the slack of the six buffers.  Linear in the bytes and in the count. */
+#define SNAPPY_AMD_LONG_RECORD_MAX (1u << 30)
+/* Capacity d_out must have: total + total/32 + 32 (count + total/65536) + 16
+ * (the one-unit bound of the short call, taken per block). */
+size_t snappy_amd_max_long_records_output(size_t total_bytes, size_t count);
+size_t snappy_amd_max_long_records_scratch(size_t total_bytes, size_t count);
+size_t snappy_amd_max_records_index(size_t total_bytes, size_t count); /* entries */
+
+/* compress_records_device for long records.  Statuses and packing as there:
+ * len > SNAPPY_AMD_LONG_RECORD_MAX is SNAPPY_AMD_ERR_UNSUPPORTED (checked before
+ * the range), a range that leaves [0, in_bytes) SNAPPY_AMD_ERR_ARG; a refused
+ * record writes 0 bytes, none of its bytes is loaded, it owns one table entry
+ * (0), and its neighbours are compressed as usual.  d_index (may be NULL: no
+ * table is written) gets the block tables, index_cap = the entries it can hold.
+ * out_cap below snappy_amd_max_long_records_output(sum of the accepted lengths,
+ * count), or index_cap below the entries needed: SNAPPY_AMD_ERR_CAPACITY, nothing
+ * written.  Synchronises twice: for the plan's totals and for *out_len. */
+int snappy_amd_compress_long_records_device(snappy_amd_ctx *ctx, const void *d_in, size_t in_bytes,
+                                            const uint64_t *d_in_off_len, size_t count, void *d_out, size_t out_cap,
+                                            uint64_t *d_offsets, uint64_t *d_index, size_t index_cap,
+                                            int32_t *d_status, size_t *out_len);
+
+/* The block tables of records of any writer (d_out_off_len: the decoded lengths;
+ * its offsets are not read).  Each record of two or more blocks is walked by one
+ * wave inside its own compressed range; its preamble must equal its decoded
+ * length (SNAPPY_AMD_ERR_HEADER).  d_status (may be NULL) gets 0 or the
+ * record's failure: HEADER, TRUNCATED, OVERRUN, UNSUPPORTED as
+ * snappy_amd_index_device reports them, and the range checks of the decode call.
+ * A failing record's entries are undefined.  index_cap below the entries needed:
+ * SNAPPY_AMD_ERR_CAPACITY.  Synchronises once (the plan's totals); the walk
+ * itself is queued. */
+int snappy_amd_records_index_device(snappy_amd_ctx *ctx, const void *d_comp, size_t comp_bytes,
+                                    const uint64_t *d_comp_off_len, size_t count, const uint64_t *d_out_off_len,
+                                    uint64_t *d_index, size_t index_cap, int32_t *d_status);
+
+/* decompress_records_device for long records.  For every record the bytes and
+ * the status are those of snappy_amd_index_device followed by
+ * snappy_amd_decompress_device(SNAPPY_AMD_SINGLE) on the same compressed bytes:
+ * elements may straddle blocks, copies may reach earlier blocks of the same
+ * record (a second, ordered pass inside the record); a copy reaching before the
+ * record's first output byte is SNAPPY_AMD_ERR_OFFSET.  The preamble must equal
+ * out_len_i (SNAPPY_AMD_ERR_HEADER).  d_index = the tables (compress's, or
+ * records_index_device's), or NULL: they are built in scratch, and an index
+ * failure is the record's status with nothing of it decoded.  A table whose last
+ * entry of a record is not its compressed length, or with another entry past
+ * it, is SNAPPY_AMD_ERR_INDEX before any load; an entry moved off an element
+ * boundary is SNAPPY_AMD_ERR_INDEX as in the SINGLE layout.  Checked before any
+ * byte of a record is loaded or stored, with the short call's meanings:
+ * out_len_i > SNAPPY_AMD_LONG_RECORD_MAX, a compressed range outside comp_bytes,
+ * an output range outside out_bytes, an empty compressed range.  No read leaves
+ * the record's compressed range (beyond the aligned dword holding its first
+ * byte); a failing record may leave part of its own output range written, never
+ * a byte outside it.  d_status, sync and the first failure as in the short
+ * call; the call synchronises once in any case, for the plan's totals. */
+int snappy_amd_decompress_long_records_device(snappy_amd_ctx *ctx, const void *d_comp, size_t comp_bytes,
+                                              const uint64_t *d_comp_off_len, size_t count, void *d_out,
+                                              size_t out_bytes, const uint64_t *d_out_off_len, const uint64_t *d_index,
+                                              int32_t *d_status, int sync);
+
 /* ---- Snappy framing format (framing_format.txt of google/snappy) -------- */
 /* The file format other Snappy tools exchange: the 10-byte stream identifier
  * ff 06 00 00 "sNaPpY", then chunks -- a type byte, a 24-bit little-endian

@@ -32,7 +32,8 @@
 #endif
     if (blockIdx.y == 0) {
         if (hdr_mode == SNAPPY_HDR_EVERY_UNIT) varint_put(L, dst, lane);
-        else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && u == 0) varint_put(header_value, dst, lane);
+        // (K2_RECORDS: the entry point says which units are first ones -- block 0 of a long record)
+        else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && (K2_RECORDS || u == 0)) varint_put(header_value, dst, lane);
     }
     // the next pass's token words (and the next segment's record) are loaded one
     // pass ahead, so their round trip overlaps this pass's literal loads

@@ -12,6 +12,8 @@
 #define SNAPPY_HDR_NONE 0        // a SINGLE-layout shard continuing a stream
 #define SNAPPY_HDR_FIRST_UNIT 1  // unit 0 = start of a SINGLE stream
 #define SNAPPY_HDR_EVERY_UNIT 2  // STREAMS layout: every unit is a stream
+// (long records pass FIRST_UNIT for block 0 of a record and NONE for its other blocks:
+// at the record entry points the mode is the unit's own, whatever its number)
 
 // per-unit status values (same numbers as SNAPPY_AMD_ERR_* in snappy_amd.h)
 #define SNAPPY_ST_OK 0
@@ -102,6 +104,54 @@ __global__ void kr4_decode_records(const uint8_t *__restrict__ comp, uint32_t bi
                                    const uint64_t *__restrict__ comp_off_len, uint8_t *__restrict__ out,
                                    uint64_t out_bytes, const uint64_t *__restrict__ out_off_len,
                                    int32_t *__restrict__ status, unsigned long long *__restrict__ first);
+
+// ---- long records (snappy_long_records.hip): records of 0 .. 2^30 bytes, each
+// ceil(L / SNAPPY_BLOCK) blocks of one stream.  A unit is one block (or an empty
+// record); the units of a batch are numbered in record order: record r owns
+// units [ubase[r], ubase[r + 1]), urec[u] is unit u's record, and its table
+// slice (nblk + 1 entries of the SINGLE index format) starts at tbase[r].
+// K1r / K1r64 over one class's unit list: workgroup b matches unit list[b], whose
+// scratch is at scratch + sbase[unit]; block 0 accounts for the record's preamble
+__global__ void kr1_match_lunits(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                 const uint32_t *__restrict__ list, const uint32_t *__restrict__ urec,
+                                 const uint64_t *__restrict__ ubase, const uint64_t *__restrict__ sbase,
+                                 uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                 uint32_t *__restrict__ sizes);
+__global__ void kr1_match_lunits64(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                   const uint32_t *__restrict__ list, const uint32_t *__restrict__ urec,
+                                   const uint64_t *__restrict__ ubase, const uint64_t *__restrict__ sbase,
+                                   uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                   uint32_t *__restrict__ sizes);
+// K2 over every unit (grid x = units, y = waves per unit); offsets = K3 over the unit sizes
+__global__ void kr2_emit_lunits(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                const uint32_t *__restrict__ urec, const uint64_t *__restrict__ ubase,
+                                const uint64_t *__restrict__ sbase, const uint32_t *__restrict__ scratch,
+                                const uint32_t *__restrict__ ntok, const uint64_t *__restrict__ offsets,
+                                uint8_t *__restrict__ out);
+// The one-wave walk of k5_index_stream over every record of two or more blocks
+// (grid x = records): record r's table slice from its own compressed range; the
+// preamble must equal its decoded length.  rstatus[r] (the plan's word, 0 where
+// the record passed the range checks) gets the walk's failure.  Records of at
+// most one block get their entries (0, and the compressed length) without a walk.
+__global__ void kr5_index_lrecords(const uint8_t *__restrict__ comp, const uint64_t *__restrict__ comp_off_len,
+                                   const uint64_t *__restrict__ out_off_len, const uint64_t *__restrict__ tbase,
+                                   uint64_t *__restrict__ index, int32_t *__restrict__ rstatus);
+// What the two K4 entry points of long records read: every pointer is the batch's
+struct K4LongArgs {
+    const uint8_t *comp;            // 4-byte aligned; the records' offsets count from comp + bias
+    uint32_t bias;
+    const uint64_t *comp_off_len, *out_off_len;
+    const uint32_t *urec;           // unit -> record
+    const uint64_t *ubase, *tbase;  // record -> first unit, first table entry
+    const uint64_t *index;          // the tables, packed
+    const int32_t *rstatus;         // the records' status after the plan and the index (< 0: nothing is decoded)
+    int32_t *ustatus;               // record r: max(nblk, 1) + 2 words at ubase[r] + 2 r (units, ticket, defer flag)
+    uint32_t *defer;                // the batch's flag: some record has work for pass 2
+    uint8_t *out;
+};
+// K4 pass 1 and pass 2 (grid x = units): k4_body with the SINGLE-layout arguments of the unit's record
+__global__ void kr4_decode_lunits(const K4LongArgs a);
+__global__ void kr4_back_lunits(const K4LongArgs a);
 
 #ifndef SNAPPY_K5_CHUNK
 #define SNAPPY_K5_CHUNK 16384

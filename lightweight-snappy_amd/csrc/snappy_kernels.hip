@@ -15,6 +15,10 @@
 //                          and K4 pass 1 bodies over a record batch -- each unit's
 //                          place comes from tables, not from u * unit
 //                          (snappy_records.hip holds the plan pass and the launches)
+//   KL  kr1_match_lunits(64), kr2_emit_lunits, kr5_index_lrecords, kr4_decode_lunits,
+//       kr4_back_lunits:   the same bodies, the K5 walk and K4 pass 2 over the blocks
+//                          of long records -- a unit is one block of one record
+//                          (snappy_long_records.hip holds the plan, the expansion and the launches)
 //
 // The hash table holds block-relative positions; 0 is a valid candidate,
 // exactly as in the reference (snappy_compression.c:259-265).
@@ -623,7 +627,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     // and the end of the last flushed token; K2 segments start every kK2Seg tokens
     uint32_t acc = 0, cend = 0;
     if (hdr_mode == SNAPPY_HDR_EVERY_UNIT) acc = varint_len(L);
-    else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && u == 0) acc = varint_len(header_value);
+    // (REC: the entry point says which units are first ones -- block 0 of a long record)
+    else if (hdr_mode == SNAPPY_HDR_FIRST_UNIT && (REC || u == 0)) acc = varint_len(header_value);
     // K2 segment k (tokens kK2Seg k ..): its output offset in the unit and the
     // input position where its first token's literal starts
     uint32_t *const segu = REC ? rec.segu : seg_off + 2 * (uint64_t)u * segs;
@@ -1841,6 +1846,64 @@ __global__ __launch_bounds__(64, 3) void kr1_match_records64(const uint8_t *__re
 }
 #endif
 
+// Long records (snappy_long_records.hip): workgroup b takes unit list[b], block
+// u - ubase[r] of record r = urec[u]: its source 65,536 bytes a block into the
+// record, its length what the record has left there (the expansion pass let only
+// 1 .. 32,768 into K1r's list: a record's last block, or a short record), its
+// scratch at scratch + sbase[u].  ntok_out and sizes are indexed by the flat unit
+// number.  Block 0 counts the record's preamble (the record's length), the others
+// none.  Every field is made scalar before the body sees it.
+template <bool BIG>
+__device__ __forceinline__ void kr1_lunit(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off_len,
+                                          const uint32_t *__restrict__ list, const uint32_t *__restrict__ urec,
+                                          const uint64_t *__restrict__ ubase, const uint64_t *__restrict__ sbase,
+                                          uint32_t *__restrict__ scratch, uint32_t *__restrict__ ntok_out,
+                                          uint32_t *__restrict__ sizes)
+{
+    K1Record rec;
+    rec.u = rfl(list[blockIdx.x]);
+    const uint32_t r = rfl(urec[rec.u]);
+    const uint32_t blk = rec.u - rfl((uint32_t)ubase[r]);
+    const uint64_t len = rfl64(off_len[2 * (uint64_t)r + 1]);
+    const uint64_t at = (uint64_t)blk * SNAPPY_BLOCK;
+    rec.L = (uint32_t)(len - at < SNAPPY_BLOCK ? len - at : SNAPPY_BLOCK);
+    rec.src = in + rfl64(off_len[2 * (uint64_t)r]) + at;
+    const uint32_t tok_cap = records_tok_cap(rec.L);
+    rec.tok = scratch + rfl64(sbase[rec.u]);
+    rec.tok_full = rec.tok + tok_cap;
+    rec.segu = rec.tok_full + tok_cap;
+    k1r_body<BIG, true>(nullptr, 0, 0, blk == 0 ? SNAPPY_HDR_FIRST_UNIT : SNAPPY_HDR_NONE, len, nullptr, 0, ntok_out,
+                        sizes, nullptr, 0, rec);
+}
+
+#if SNAPPY_TU_COMPRESS
+__global__ __launch_bounds__(64, 3) void kr1_match_lunits(const uint8_t *__restrict__ in,
+                                                           const uint64_t *__restrict__ off_len,
+                                                           const uint32_t *__restrict__ list,
+                                                           const uint32_t *__restrict__ urec,
+                                                           const uint64_t *__restrict__ ubase,
+                                                           const uint64_t *__restrict__ sbase,
+                                                           uint32_t *__restrict__ scratch,
+                                                           uint32_t *__restrict__ ntok_out,
+                                                           uint32_t *__restrict__ sizes)
+{
+    kr1_lunit<false>(in, off_len, list, urec, ubase, sbase, scratch, ntok_out, sizes);
+}
+
+__global__ __launch_bounds__(64, 3) void kr1_match_lunits64(const uint8_t *__restrict__ in,
+                                                             const uint64_t *__restrict__ off_len,
+                                                             const uint32_t *__restrict__ list,
+                                                             const uint32_t *__restrict__ urec,
+                                                             const uint64_t *__restrict__ ubase,
+                                                             const uint64_t *__restrict__ sbase,
+                                                             uint32_t *__restrict__ scratch,
+                                                             uint32_t *__restrict__ ntok_out,
+                                                             uint32_t *__restrict__ sizes)
+{
+    kr1_lunit<true>(in, off_len, list, urec, ubase, sbase, scratch, ntok_out, sizes);
+}
+#endif
+
 // ---------------------------------------------------------------------------
 // K2: token list -> Snappy bytes at the unit's final offset (after K3's scan),
 // one wave per unit, one token per lane: literal header + literal bytes (read
@@ -2078,11 +2141,14 @@ __global__ __launch_bounds__(64, 6) void k2_emit_units(const uint8_t *__restrict
 }
 
 // K2's body over one record (`in`, `n`: the record's own start and length)
+// (hdr_mode, header_value: constants at the short records' entry point, so its
+// instructions are those of the body with SNAPPY_HDR_EVERY_UNIT written in)
 __device__ __forceinline__ void kr2_emit_one(const uint8_t *in, const K2Record rec, const uint32_t *ntok,
-                                             const uint64_t *offsets, uint8_t *out)
+                                             const uint64_t *offsets, uint8_t *out,
+                                             const uint32_t hdr_mode = SNAPPY_HDR_EVERY_UNIT,
+                                             const uint64_t header_value = 0)
 {
-    const uint64_t n = rec.L, header_value = 0;
-    const uint32_t hdr_mode = SNAPPY_HDR_EVERY_UNIT;
+    const uint64_t n = rec.L;
 #define K2_RECORDS 1
 #include "snappy_k2_emit.inc"
 #undef K2_RECORDS
@@ -2117,6 +2183,39 @@ __global__ __launch_bounds__(64, 6) void kr2_emit_records(const uint8_t *__restr
     rec.tok_full = rec.tok + tok_cap;
     rec.segu = rec.tok_full + tok_cap;
     kr2_emit_one(base + rfl64(off), rec, ntok, offsets, out);
+}
+
+// Long records: workgroup x is unit x (see kr1_lunit), y the wave of its segments.
+// Block 0 writes the record's preamble; an empty record's one unit writes the byte
+// 00 and touches neither the input nor the scratch.  Refused records own no unit.
+__global__ __launch_bounds__(64, 6) void kr2_emit_lunits(const uint8_t *__restrict__ base,
+                                                         const uint64_t *__restrict__ off_len,
+                                                         const uint32_t *__restrict__ urec,
+                                                         const uint64_t *__restrict__ ubase,
+                                                         const uint64_t *__restrict__ sbase,
+                                                         const uint32_t *__restrict__ scratch,
+                                                         const uint32_t *__restrict__ ntok,
+                                                         const uint64_t *__restrict__ offsets,
+                                                         uint8_t *__restrict__ out)
+{
+    const uint32_t u = blockIdx.x;
+    const uint32_t r = rfl(urec[u]);
+    const uint64_t sb = sbase[u];
+    const uint64_t off = off_len[2 * (uint64_t)r], len = rfl64(off_len[2 * (uint64_t)r + 1]);
+    const uint32_t blk = u - rfl((uint32_t)ubase[r]);
+    if (len == 0) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) out[offsets[u]] = 0;
+        return;
+    }
+    const uint64_t at = (uint64_t)blk * SNAPPY_BLOCK;
+    K2Record rec;
+    rec.L = (uint32_t)(len - at < SNAPPY_BLOCK ? len - at : SNAPPY_BLOCK);
+    const uint32_t tok_cap = records_tok_cap(rec.L);
+    rec.tok = scratch + rfl64(sb);
+    rec.tok_full = rec.tok + tok_cap;
+    rec.segu = rec.tok_full + tok_cap;
+    kr2_emit_one(base + rfl64(off) + at, rec, ntok, offsets, out, blk == 0 ? SNAPPY_HDR_FIRST_UNIT : SNAPPY_HDR_NONE,
+                 len);
 }
 #endif
 
@@ -2424,11 +2523,16 @@ struct K4Record {
     unsigned long long *first;  // the batch's first failure: min over (record << 8 | -status)
 };
 
-template <bool BACK, bool REC = false>
+// LONG (a block of a long record, snappy_long_records.hip): the stream is one
+// record of a batch, so the units of this stream -- status[units] and
+// status[units + 1] are pass 2's ticket counter and pass 1's defer flag -- are
+// the record's own blocks (`units`), not the grid of the launch.
+template <bool BACK, bool REC = false, bool LONG = false>
 __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const uint64_t *__restrict__ offsets,
                                         uint64_t n, uint32_t unit, uint32_t hdr_mode, uint64_t header_value,
                                         uint32_t allow_back, uint32_t bias, uint8_t *__restrict__ out,
-                                        int32_t *__restrict__ status, uint32_t u, const K4Record rec = {})
+                                        int32_t *__restrict__ status, uint32_t u, const K4Record rec = {},
+                                        const uint32_t units = 0)
 {
     static_assert(!(BACK && REC), "records are their own streams: there is no second pass");
     // copy source positions: relative to the unit start, negative = an earlier unit (pass 2 only)
@@ -3119,7 +3223,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
     } else {
         if (lane == 0) status[u] = st;
         // status[units + 1] = pass 2 has work (status[units] is pass 2's ticket counter)
-        if (st == SNAPPY_ST_DEFER && lane == 0) status[gridDim.x + 1] = 1;
+        if (st == SNAPPY_ST_DEFER && lane == 0) status[(LONG ? units : gridDim.x) + 1] = 1;
     }
 }
 
@@ -3181,6 +3285,98 @@ __global__ __launch_bounds__(64) void k4_decompress_back(const uint8_t *__restri
     if (status[u] != SNAPPY_ST_DEFER) return;
     k4_body<true>(comp, offsets, n, unit, hdr_mode, header_value, 1u, bias, out, status, u);
 }
+
+// Long records: a unit is block u - ubase[r] of record r = urec[u], and k4_body
+// gets the SINGLE-layout arguments of that one record -- its table slice as the
+// index, its decoded length as n and as the preamble's value, the 4-aligned
+// address of its first compressed byte with that byte's bias, its own output
+// start and its own status slice -- so it reaches this record's data and words
+// only: the slice's last entry bounds every read, a copy before the record's
+// first byte is a copy before the stream (ERR_OFFSET), pass 2 waits on this
+// record's blocks.
+struct K4LongUnit {
+    const uint8_t *comp;
+    const uint64_t *table;
+    uint64_t n;
+    uint32_t bias, nblk;
+    uint8_t *out;
+    int32_t *status;
+};
+
+__device__ __forceinline__ K4LongUnit k4_long_unit(const K4LongArgs &a, uint32_t r)
+{
+    const uint64_t co = rfl64(a.comp_off_len[2 * (uint64_t)r]);
+    const uint64_t oo = rfl64(a.out_off_len[2 * (uint64_t)r]), ol = rfl64(a.out_off_len[2 * (uint64_t)r + 1]);
+    const uint64_t ub = rfl64(a.ubase[r]);
+    K4LongUnit k;
+    k.comp = a.comp + ((a.bias + co) & ~3ull);
+    k.bias = (uint32_t)((a.bias + co) & 3);
+    k.table = a.index + rfl64(a.tbase[r]);
+    k.n = ol;
+    k.nblk = (uint32_t)((ol + SNAPPY_BLOCK - 1) / SNAPPY_BLOCK);
+    k.out = a.out + oo;
+    k.status = a.ustatus + ub + 2 * (uint64_t)r;
+    return k;
+}
+
+// Pass 1, one wave per unit.  A record the plan or the index refused decodes
+// nothing.  Before the first load of a unit: the record's last table entry must
+// be its compressed length and the unit's own two entries must not pass it
+// (ERR_INDEX: a caller's table that is not this record's).  An empty record's
+// one unit checks its preamble, a varint of value 0 inside the range.
+__global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_decode_lunits(const K4LongArgs a)
+{
+    const uint32_t u = blockIdx.x;
+    const uint32_t r = rfl(a.urec[u]);
+    if (rfl((uint32_t)a.rstatus[r]) != 0) return;
+    const K4LongUnit k = k4_long_unit(a, r);
+    const uint32_t blk = u - rfl((uint32_t)a.ubase[r]);
+    const uint64_t cl = rfl64(a.comp_off_len[2 * (uint64_t)r + 1]);
+    if (k.n == 0) {
+        if (threadIdx.x == 0) {
+            const uint8_t *p = k.comp + k.bias;
+            int32_t st = SNAPPY_ST_HEADER;
+            uint64_t v = 0;
+            for (uint32_t i = 0; i < 10 && i < cl; i++) {
+                const uint32_t b = p[i];
+                v |= (uint64_t)(b & 0x7F) << (7 * i);
+                if (!(b & 0x80)) { st = v == 0 ? SNAPPY_ST_OK : SNAPPY_ST_HEADER; break; }
+            }
+            k.status[0] = st;
+        }
+        return;
+    }
+    const uint64_t e0 = rfl64(k.table[blk]) & kIdxOffMask, e1 = rfl64(k.table[blk + 1]) & kIdxOffMask;
+    const uint64_t el = rfl64(k.table[k.nblk]) & kIdxOffMask;
+    if (el != cl || e0 > cl || e1 > cl) {
+        if (threadIdx.x == 0) k.status[blk] = SNAPPY_ST_INDEX;
+        return;
+    }
+    k4_body<false, false, true>(k.comp, k.table, k.n, SNAPPY_BLOCK, SNAPPY_HDR_FIRST_UNIT, k.n, 1u, k.bias, k.out,
+                                k.status, blk, {}, k.nblk);
+    // (the lane that wrote the unit's status reads it back: a deferred unit also raises the batch's flag)
+    if (threadIdx.x == 0 && k.status[blk] == SNAPPY_ST_DEFER) *a.defer = 1u;
+}
+
+// Pass 2 over all units: a wave leaves at once unless the batch and then its own
+// record have deferred units; its ticket comes from the record's own counter (as
+// many waves take one as the record has blocks, in dispatch order, so a block a
+// wave waits for is held by a wave already running or done).
+__global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_back_lunits(const K4LongArgs a)
+{
+    if (*reinterpret_cast<const volatile uint32_t *>(a.defer) == 0) return;
+    const uint32_t r = rfl(a.urec[blockIdx.x]);
+    if (rfl((uint32_t)a.rstatus[r]) != 0) return;
+    const K4LongUnit k = k4_long_unit(a, r);
+    if (k.n == 0) return;
+    if (*reinterpret_cast<const volatile int32_t *>(k.status + k.nblk + 1) == 0) return;
+    uint32_t tk = 0;
+    if (threadIdx.x == 0) tk = atomicAdd(reinterpret_cast<uint32_t *>(k.status + k.nblk), 1u);
+    const uint32_t blk = __builtin_amdgcn_readfirstlane(tk);
+    if (blk >= k.nblk || k.status[blk] != SNAPPY_ST_DEFER) return;
+    k4_body<true, false, true>(k.comp, k.table, k.n, SNAPPY_BLOCK, SNAPPY_HDR_FIRST_UNIT, k.n, 1u, k.bias, k.out,
+                               k.status, blk, {}, k.nblk);
+}
 #endif
 // ---------------------------------------------------------------------------
 // K5: block index of a SINGLE-layout stream (one wave).  The stream is
@@ -3197,10 +3393,14 @@ __device__ __forceinline__ uint32_t win_byte(uint32_t w0, uint32_t w1, uint32_t 
     return (v >> (8 * (rel & 3))) & 0xFF;
 }
 
-#if SNAPPY_TU_DECODE
-__global__ __launch_bounds__(64) void k5_index_stream(const uint8_t *__restrict__ comp, uint64_t clen,
-                                                      uint64_t *__restrict__ offsets, uint64_t max_units,
-                                                      int64_t *__restrict__ result)
+// The walk of one stream comp[0, clen) by one wave: offsets gets units + 1
+// entries (max_units = how many it can hold), *n_out the declared length,
+// *units_out its blocks.  expect != ~0: the declared length must be this value
+// (SNAPPY_ST_HEADER otherwise, before any entry is written): a record of a
+// batch, whose table slice was sized from it.
+__device__ __forceinline__ int64_t k5_walk(const uint8_t *__restrict__ comp, uint64_t clen,
+                                           uint64_t *__restrict__ offsets, uint64_t max_units, uint64_t expect,
+                                           uint64_t *n_out, uint64_t *units_out)
 {
     const uint32_t lane = threadIdx.x;
     uint64_t wbase = ~0ull;
@@ -3230,7 +3430,7 @@ __global__ __launch_bounds__(64) void k5_index_stream(const uint8_t *__restrict_
         N |= (uint64_t)(byte & 0x7F) << (7 * k);
         if (!(byte & 0x80)) { done = true; break; }
     }
-    if (!done) st = SNAPPY_ST_HEADER;
+    if (!done || (expect != ~0ull && N != expect)) st = SNAPPY_ST_HEADER;
     const uint64_t units = (N + SNAPPY_BLOCK - 1) / SNAPPY_BLOCK;
     if (st == SNAPPY_ST_OK && units >= max_units) st = SNAPPY_ST_CAPACITY;  // units + 1 entries needed
     uint64_t op = 0, unit = 0;
@@ -3278,11 +3478,56 @@ __global__ __launch_bounds__(64) void k5_index_stream(const uint8_t *__restrict_
         }
         if (op > N) { st = SNAPPY_ST_OVERRUN; break; }
     }
-    if (lane == 0) {
-        if (st == SNAPPY_ST_OK) offsets[units] = ip;
+    if (lane == 0 && st == SNAPPY_ST_OK) offsets[units] = ip;
+    *n_out = N;
+    *units_out = units;
+    return st;
+}
+
+#if SNAPPY_TU_DECODE
+__global__ __launch_bounds__(64) void k5_index_stream(const uint8_t *__restrict__ comp, uint64_t clen,
+                                                      uint64_t *__restrict__ offsets, uint64_t max_units,
+                                                      int64_t *__restrict__ result)
+{
+    uint64_t N, units;
+    const int64_t st = k5_walk(comp, clen, offsets, max_units, ~0ull, &N, &units);
+    if (threadIdx.x == 0) {
         result[0] = st;
         result[1] = (int64_t)N;
         result[2] = (int64_t)units;
+    }
+}
+
+// Long records: the walk over record r = blockIdx.x, bounded by its own
+// compressed range.  A record the plan refused is left alone.  At most one block:
+// the entries 0 and the compressed length, no walk (K4 checks the preamble and
+// that the block's chain ends there).  A walk that fails is the record's status.
+// The last entry of a passing walk is where the stream's elements end; bytes a
+// writer left after them belong to no block, and K4 bounds its reads by the
+// compressed length, so the entry written is that length.
+__global__ __launch_bounds__(64) void kr5_index_lrecords(const uint8_t *__restrict__ comp,
+                                                         const uint64_t *__restrict__ comp_off_len,
+                                                         const uint64_t *__restrict__ out_off_len,
+                                                         const uint64_t *__restrict__ tbase,
+                                                         uint64_t *__restrict__ index, int32_t *__restrict__ rstatus)
+{
+    const uint32_t r = blockIdx.x;
+    if (rfl((uint32_t)rstatus[r]) != 0) return;
+    const uint64_t co = rfl64(comp_off_len[2 * (uint64_t)r]), cl = rfl64(comp_off_len[2 * (uint64_t)r + 1]);
+    const uint64_t ol = rfl64(out_off_len[2 * (uint64_t)r + 1]);
+    uint64_t *const table = index + rfl64(tbase[r]);
+    if (ol <= SNAPPY_BLOCK) {
+        if (threadIdx.x == 0) {
+            table[0] = 0;
+            if (ol) table[1] = cl;
+        }
+        return;
+    }
+    uint64_t N, units;
+    const int64_t st = k5_walk(comp + co, cl, table, (ol + SNAPPY_BLOCK - 1) / SNAPPY_BLOCK + 1, ol, &N, &units);
+    if (threadIdx.x == 0) {
+        if (st != SNAPPY_ST_OK) rstatus[r] = (int32_t)st;
+        else table[units] = cl;
     }
 }
 #endif

@@ -42,6 +42,7 @@ IDX_MAGIC = 0x3158444941504E53  # b"SNPAIDX1" as a little-endian u64
 
 BLOCK = 65536
 RECORD_MAX = 65536  # decoded bytes of one record of a record batch
+LONG_RECORD_MAX = 1 << 30  # of one record of the long-record calls
 SINGLE = 0
 STREAMS = 1
 NO_PREAMBLE = 1
@@ -155,6 +156,19 @@ _SIGS = {
     "snappy_amd_decompress_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                                         _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                                         _c.c_void_p, _c.c_int]),
+    # long records
+    "snappy_amd_max_long_records_output": (_c.c_size_t, [_c.c_size_t, _c.c_size_t]),
+    "snappy_amd_max_long_records_scratch": (_c.c_size_t, [_c.c_size_t, _c.c_size_t]),
+    "snappy_amd_max_records_index": (_c.c_size_t, [_c.c_size_t, _c.c_size_t]),
+    "snappy_amd_compress_long_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                           _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                           _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                           _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_records_index_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                   _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "snappy_amd_decompress_long_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                             _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                             _c.c_void_p, _c.c_void_p, _c.c_int]),
     "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
     "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
 }
@@ -363,6 +377,30 @@ def max_records_output(total_bytes: int, count: int) -> int:
 def max_records_scratch(total_bytes: int, count: int) -> int:
     """Upper bound of Codec.device_bytes() after a compress_records call."""
     return lib().snappy_amd_max_records_scratch(total_bytes, count)
+
+
+def max_long_records_output(total_bytes: int, count: int) -> int:
+    """Capacity the output of a compress_long_records call must have."""
+    return lib().snappy_amd_max_long_records_output(total_bytes, count)
+
+
+def max_long_records_scratch(total_bytes: int, count: int) -> int:
+    """Upper bound of Codec.device_bytes() after a long-records call."""
+    return lib().snappy_amd_max_long_records_scratch(total_bytes, count)
+
+
+def max_records_index(total_bytes: int, count: int) -> int:
+    """Entries that hold the block tables of `count` records of `total_bytes`."""
+    return lib().snappy_amd_max_records_index(total_bytes, count)
+
+
+def records_table_bases(lengths):
+    """Where each record's block table starts in the packed tables: record i has
+    ceil(L_i / 65536) + 1 entries -> list of count + 1 positions."""
+    pos = [0]
+    for n in lengths:
+        pos.append(pos[-1] + (int(n) + BLOCK - 1) // BLOCK + 1)
+    return pos
 
 
 def read_index(data: bytes):
@@ -714,6 +752,131 @@ class Codec:
         flat = out.cpu().numpy().tobytes()
         return [flat[int(ooffs[i]): int(ooffs[i] + lens[i])] for i in range(len(records))]
 
+    # long records (0 .. 2^30 bytes each, many blocks) ---------------------------
+    def compress_long_records_tensor(self, base, off_len, out=None, want_status: bool = True, check: bool = False,
+                                     want_index: bool = True, index=None):
+        """compress_records_tensor for records of 0..2^30 bytes -> (payload tensor,
+        offsets tensor of count + 1, status tensor of count, block tables).  The
+        tables (int64 tensor; None with want_index=False) hold ceil(L/65536) + 1
+        entries per record, packed in record order (one entry for a refused record)."""
+        assert base.is_cuda and base.dtype == torch.uint8 and base.is_contiguous()
+        assert off_len.is_cuda and off_len.dtype == torch.int64 and off_len.is_contiguous()
+        count = off_len.numel() // 2
+        if out is None or (want_index and index is None):
+            # (an upper bound of the accepted bytes without a second read-back: each record min(length, cap))
+            total = int(off_len.view(-1, 2)[:, 1].clamp(0, LONG_RECORD_MAX).sum().item()) if count else 0
+            if out is None:
+                out = torch.empty(max_long_records_output(total, count), dtype=torch.uint8, device=base.device)
+            if want_index and index is None:
+                index = torch.empty(max(max_records_index(total, count), 1), dtype=torch.int64, device=base.device)
+        if not want_index:
+            index = None
+        offs = torch.empty(count + 1, dtype=torch.int64, device=base.device)
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=base.device) if want_status else None
+        got = ctypes.c_size_t(0)
+        self._bind_stream()
+        rc = lib().snappy_amd_compress_long_records_device(
+            self._h, ctypes.c_void_p(base.data_ptr()), base.numel(), ctypes.c_void_p(off_len.data_ptr()), count,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(offs.data_ptr()),
+            ctypes.c_void_p(index.data_ptr()) if index is not None else None,
+            index.numel() if index is not None else 0,
+            ctypes.c_void_p(status.data_ptr()) if want_status else None, ctypes.byref(got))
+        self.last_records_status = rc
+        # a refusal is reported per record; anything else (capacity, device, arguments) failed the call
+        if rc != OK and (check or rc not in (ERR_UNSUPPORTED, ERR_ARG) or count == 0):
+            raise SnappyError(rc, "compress_long_records_device")
+        return out[: got.value], offs, (status[:count] if want_status else None), index
+
+    def records_index_tensor(self, comp, comp_off_len, out_lens, index=None):
+        """The block tables of the records of `comp` (comp_off_len pairs) whose
+        decoded lengths are out_lens (int64 CUDA tensor of count lengths, or of
+        (offset, length) pairs) -> (tables tensor, int32 status tensor)."""
+        assert comp.is_cuda and comp.dtype == torch.uint8 and comp_off_len.is_cuda and comp_off_len.dtype == torch.int64
+        assert out_lens.is_cuda and out_lens.dtype == torch.int64
+        count = comp_off_len.numel() // 2
+        if out_lens.numel() == count and count:
+            out_lens = torch.stack([torch.zeros_like(out_lens.view(-1)), out_lens.view(-1)], dim=1).reshape(-1)
+        assert out_lens.numel() == 2 * count
+        out_lens = out_lens.contiguous()
+        if index is None:
+            total = int(out_lens.view(-1, 2)[:, 1].clamp(0, LONG_RECORD_MAX).sum().item()) if count else 0
+            index = torch.empty(max(max_records_index(total, count), 1), dtype=torch.int64, device=comp.device)
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=comp.device)
+        self._bind_stream()
+        _check(lib().snappy_amd_records_index_device(
+            self._h, ctypes.c_void_p(comp.data_ptr()), comp.numel(), ctypes.c_void_p(comp_off_len.data_ptr()), count,
+            ctypes.c_void_p(out_lens.data_ptr()), ctypes.c_void_p(index.data_ptr()), index.numel(),
+            ctypes.c_void_p(status.data_ptr())), "records_index_device")
+        return index, status[:count]
+
+    def decompress_long_records_tensor(self, comp, comp_off_len, out, out_off_len, index=None,
+                                       want_status: bool = True, check: bool = False):
+        """decompress_records_tensor for records of 0..2^30 bytes; index = the block
+        tables (compress_long_records_tensor's or records_index_tensor's), or None:
+        they are built in scratch -> int32 status tensor."""
+        assert comp.is_cuda and comp.dtype == torch.uint8 and out.is_cuda and out.dtype == torch.uint8
+        assert comp_off_len.dtype == torch.int64 and out_off_len.dtype == torch.int64
+        assert comp_off_len.numel() == out_off_len.numel()
+        assert index is None or (index.is_cuda and index.dtype == torch.int64)
+        count = comp_off_len.numel() // 2
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=comp.device) if want_status else None
+        self._bind_stream()
+        rc = lib().snappy_amd_decompress_long_records_device(
+            self._h, ctypes.c_void_p(comp.data_ptr()), comp.numel(), ctypes.c_void_p(comp_off_len.data_ptr()), count,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(out_off_len.data_ptr()),
+            ctypes.c_void_p(index.data_ptr()) if index is not None else None,
+            ctypes.c_void_p(status.data_ptr()) if want_status else None, 1)
+        self.last_records_status = rc
+        if rc != OK and (check or rc in (ERR_DEVICE, ERR_ARG)):
+            raise SnappyError(rc, "decompress_long_records_device")
+        return status[:count] if want_status else None
+
+    def compress_long_records(self, records) -> list:
+        """list of bytes-like records (each 0..2^30 bytes) -> list of their raw
+        Snappy streams: packed, uploaded, compressed in one call."""
+        import numpy as np
+        records = [bytes(r) for r in records]
+        if not records:
+            return []
+        lens = np.array([len(r) for r in records], dtype=np.int64)
+        if int(lens.max()) > LONG_RECORD_MAX:
+            raise SnappyError(ERR_UNSUPPORTED, f"compress_long_records: record {int(np.argmax(lens > LONG_RECORD_MAX))}")
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        dev = torch.device("cuda", self.device)
+        base = self._upload(b"".join(records), dev)
+        off_len = torch.from_numpy(np.stack([offs, lens], axis=1).reshape(-1).copy()).to(dev)
+        payload, o, _, _ = self.compress_long_records_tensor(base, off_len, check=True, want_index=False)
+        o, p = o.cpu().numpy(), payload.cpu().numpy().tobytes()
+        return [p[int(o[i]): int(o[i + 1])] for i in range(len(records))]
+
+    def decompress_long_records(self, records) -> list:
+        """list of raw Snappy streams (each up to 2^30 decoded bytes) -> list of
+        their decoded bytes: one length call and one decode call (the block tables
+        are built in scratch); raises SnappyError with the first failing record's code."""
+        import numpy as np
+        records = [bytes(r) for r in records]
+        if not records:
+            return []
+        clens = np.array([len(r) for r in records], dtype=np.int64)
+        coffs = np.concatenate(([0], np.cumsum(clens)[:-1])).astype(np.int64)
+        dev = torch.device("cuda", self.device)
+        comp = self._upload(b"".join(records), dev)
+        c_ol = torch.from_numpy(np.stack([coffs, clens], axis=1).reshape(-1).copy()).to(dev)
+        lens, st = self.records_length_tensor(comp, c_ol)
+        lens, st = lens.cpu().numpy(), st.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            raise SnappyError(int(st[bad[0]]), f"decompress_long_records: record {int(bad[0])}")
+        big = np.nonzero((lens > LONG_RECORD_MAX) | (lens < 0))[0]
+        if big.size:
+            raise SnappyError(ERR_UNSUPPORTED, f"decompress_long_records: record {int(big[0])}")
+        ooffs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        out = torch.empty(max(int(lens.sum()), 1), dtype=torch.uint8, device=dev)[: int(lens.sum())]
+        o_ol = torch.from_numpy(np.stack([ooffs, lens], axis=1).reshape(-1).copy()).to(dev)
+        self.decompress_long_records_tensor(comp, c_ol, out, o_ol, want_status=False, check=True)
+        flat = out.cpu().numpy().tobytes()
+        return [flat[int(ooffs[i]): int(ooffs[i] + lens[i])] for i in range(len(records))]
+
 
 def compress_records(records, device: int = 0) -> list:
     """Codec(device).compress_records(records) on a context of its own."""
@@ -729,5 +892,32 @@ def decompress_records(records, device: int = 0) -> list:
     c = Codec(device)
     try:
         return c.decompress_records(records)
+    finally:
+        c.close()
+
+
+def compress_long_records(records, device: int = 0) -> list:
+    """Codec(device).compress_long_records(records) on a context of its own
+    (the records are checked first: an empty list needs no device)."""
+    records = [bytes(r) for r in records]
+    if not records:
+        return []
+    c = Codec(device)
+    try:
+        return c.compress_long_records(records)
+    finally:
+        c.close()
+
+
+def decompress_long_records(records, device: int = 0) -> list:
+    """Codec(device).decompress_long_records(records) on a context of its own."""
+    records = [bytes(r) for r in records]
+    if not records:
+        return []
+    if any(len(r) == 0 for r in records):
+        raise SnappyError(ERR_HEADER, f"decompress_long_records: record {[len(r) for r in records].index(0)}")
+    c = Codec(device)
+    try:
+        return c.decompress_long_records(records)
     finally:
         c.close()

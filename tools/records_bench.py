@@ -9,11 +9,21 @@ process.  Compress and decode each:
   c  a seeded log-uniform mix of 64 B .. 64 KiB records, N bytes in all
   d  4 KiB records
 
+and the long-record calls:
+
+  e  1 MiB records                 \
+  f  256 KiB records                >  vs  the SINGLE call on the same N bytes
+  g  a seeded log-uniform mix of 64 B .. 4 MiB records  /
+
 The STREAMS calls are the yardstick of a and b (their min..max is the spread a
-difference has to exceed); c and d have no fixed-layout counterpart.
+difference has to exceed); c and d have no fixed-layout counterpart.  The
+yardstick of e, f and g is the SINGLE call in the same round: its compress for the
+long compress, its decode for the long decode with compress's tables, and
+snappy_amd_index_device + its decode for the long decode that builds the tables
+(NULL).  The walk a NULL decode adds is also reported per record and per GiB.
 
 Prints one JSON line and writes it to profiles/<tag>.json when a tag is given:
-    python tools/records_bench.py [n_bytes] [reps] [tag]
+    python tools/records_bench.py [n_bytes] [reps] [tag] [legs, default abcdefg]
 Run under rocprofv3 --kernel-trace --stats (a run of its own) for per-kernel times."""
 import json
 import os
@@ -30,6 +40,8 @@ import snappy_amd  # noqa: E402
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 30
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 11
 tag = sys.argv[3] if len(sys.argv) > 3 else ""
+which = sys.argv[4] if len(sys.argv) > 4 else "abcdefg"
+LONG = "efg"
 
 host = np.empty(n, dtype=np.uint8)
 datagen.fill(host, "T", 1234, threads=16)
@@ -46,9 +58,9 @@ def uniform(ln):
     return np.stack([offs, np.minimum(ln, n - offs)], axis=1)
 
 
-def log_uniform(seed=1234):
+def log_uniform(seed=1234, hi=65536):
     rng = np.random.default_rng(seed)
-    lens = np.exp(rng.uniform(np.log(64), np.log(65536), size=n // 64 + 1)).astype(np.int64)
+    lens = np.exp(rng.uniform(np.log(64), np.log(hi), size=n // 64 + 1)).astype(np.int64)
     ends = np.cumsum(lens)
     k = int(np.searchsorted(ends, n)) + 1
     lens = lens[:k]
@@ -56,17 +68,23 @@ def log_uniform(seed=1234):
     return np.stack([np.concatenate(([0], ends[:k - 1])), lens], axis=1)
 
 
-legs = {"a": uniform(32768), "b": uniform(65536), "c": log_uniform(), "d": uniform(4096)}
-legs = {k: v[v[:, 1] > 0] for k, v in legs.items()}
+legs = {"a": uniform(32768), "b": uniform(65536), "c": log_uniform(), "d": uniform(4096),
+        "e": uniform(1 << 20), "f": uniform(256 << 10), "g": log_uniform(4321, 4 << 20)}
+legs = {k: v[v[:, 1] > 0] for k, v in legs.items() if k in which}
 max_count = max(len(v) for v in legs.values())
-out = torch.empty(snappy_amd.max_records_output(n, max_count), dtype=torch.uint8, device="cuda")
+out = torch.empty(max(snappy_amd.max_records_output(n, max_count), snappy_amd.max_long_records_output(n, max_count),
+                      codec.max_output(n, snappy_amd.BLOCK, snappy_amd.SINGLE)), dtype=torch.uint8, device="cuda")
 back = torch.empty(n, dtype=torch.uint8, device="cuda")
 dev = {}
 for k, v in legs.items():
     dev[k] = {"ol": torch.from_numpy(v.reshape(-1).copy()).cuda(), "count": len(v),
               "offs": torch.empty(len(v) + 1, dtype=torch.int64, device="cuda"),
               "col": torch.empty(2 * len(v), dtype=torch.int64, device="cuda"), "clen": 0}
-state = {}
+    if k in LONG:
+        dev[k]["index"] = torch.empty(snappy_amd.max_records_index(n, len(v)), dtype=torch.int64, device="cuda")
+units = (n + snappy_amd.BLOCK - 1) // snappy_amd.BLOCK
+state = {"single_offs": torch.empty(units + 1, dtype=torch.int64, device="cuda"),
+         "single_index": torch.empty(units + 1, dtype=torch.int64, device="cuda")}
 
 
 def compress_records(k):
@@ -83,6 +101,58 @@ def decode_records(k):
     snappy_amd._check(lib.snappy_amd_decompress_records_device(h, vp(out.data_ptr()), d["clen"], vp(d["col"].data_ptr()),
                                                                d["count"], vp(back.data_ptr()), n, vp(d["ol"].data_ptr()),
                                                                None, 1), "decompress_records_device")
+
+
+def compress_long(k):
+    d = dev[k]
+    got = ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_compress_long_records_device(
+        h, vp(x.data_ptr()), n, vp(d["ol"].data_ptr()), d["count"], vp(out.data_ptr()), out.numel(),
+        vp(d["offs"].data_ptr()), vp(d["index"].data_ptr()), d["index"].numel(), None, ct.byref(got)),
+        "compress_long_records_device")
+    d["clen"] = got.value
+
+
+def decode_long(k, with_table):
+    d = dev[k]
+    snappy_amd._check(lib.snappy_amd_decompress_long_records_device(
+        h, vp(out.data_ptr()), d["clen"], vp(d["col"].data_ptr()), d["count"], vp(back.data_ptr()), n,
+        vp(d["ol"].data_ptr()), vp(d["index"].data_ptr()) if with_table else None, None, 1),
+        "decompress_long_records_device")
+
+
+def compress_single():
+    state["slen"] = codec.compress_ptr(x.data_ptr(), n, snappy_amd.BLOCK, snappy_amd.SINGLE, out.data_ptr(),
+                                       state["single_offs"].data_ptr())
+
+
+def decode_single():
+    codec.decompress_ptr(out.data_ptr(), state["single_offs"].data_ptr(), n, snappy_amd.BLOCK, snappy_amd.SINGLE,
+                         back.data_ptr())
+
+
+def index_single():
+    codec.index_ptr(out.data_ptr(), state["slen"], state["single_index"].data_ptr(), units + 1)
+
+
+def long_round(k, r):
+    """one round of a long-record leg and of its yardsticks -> {name: ms}"""
+    d = dev[k]
+    t = {"compress_long": timed(compress_long, k)}
+    o = d["offs"]
+    d["col"].copy_(torch.stack([o[:-1], o[1:] - o[:-1]], dim=1).reshape(-1))
+    for name, with_table in (("decode_long_table", True), ("decode_long_null", False)):
+        if r == 1:
+            back.zero_()
+        t[name] = timed(decode_long, k, with_table)
+        if r == 1:
+            assert torch.equal(back, x), f"leg {k}: {name} round trip failed"
+    t["compress_single"] = timed(compress_single)
+    t["decode_single"] = timed(decode_single)
+    t["index_single"] = timed(index_single)
+    if r == 1:
+        assert torch.equal(state["single_index"], state["single_offs"])
+    return t
 
 
 def compress_streams(chunk):
@@ -109,7 +179,13 @@ def median(v):
 ms = {}
 with torch.cuda.stream(stream):
     for r in range(reps + 2):  # two warm-up rounds (code objects, scratch growth)
-        for k in "abcd":
+        for k in legs:
+            if k in LONG:
+                t = long_round(k, r)
+                if r >= 2:
+                    for name, v in t.items():
+                        ms.setdefault(f"{k}_{name}", []).append(v)
+                continue
             d = dev[k]
             chunk = {"a": 32768, "b": 65536}.get(k)
             t = {"compress_records": timed(compress_records, k)}
@@ -139,13 +215,21 @@ stream.synchronize()
 held = codec.device_bytes()
 codec.close()
 med = {k: median(v) for k, v in ms.items()}
-res = {"n": n, "reps": reps, "records": {k: dev[k]["count"] for k in "abcd"},
-       "compressed_bytes": {k: dev[k]["clen"] for k in "abcd"}, "device_bytes": held, "median_ms": med,
-       "a_compress_ratio": med["a_compress_records"] / med["a_compress_streams"],
-       "a_decode_ratio": med["a_decode_records"] / med["a_decode_streams"],
-       "b_compress_ratio": med["b_compress_records"] / med["b_compress_streams"],
-       "b_decode_ratio": med["b_decode_records"] / med["b_decode_streams"],
+res = {"n": n, "reps": reps, "records": {k: dev[k]["count"] for k in legs},
+       "compressed_bytes": {k: dev[k]["clen"] for k in legs}, "device_bytes": held, "median_ms": med,
        "min_max_ms": {k: [min(v), max(v)] for k, v in ms.items()}}
+for k in legs:
+    if k in "ab":
+        res[f"{k}_compress_ratio"] = med[f"{k}_compress_records"] / med[f"{k}_compress_streams"]
+        res[f"{k}_decode_ratio"] = med[f"{k}_decode_records"] / med[f"{k}_decode_streams"]
+    if k in LONG:
+        res[f"{k}_compress_ratio"] = med[f"{k}_compress_long"] / med[f"{k}_compress_single"]
+        res[f"{k}_decode_table_ratio"] = med[f"{k}_decode_long_table"] / med[f"{k}_decode_single"]
+        res[f"{k}_decode_null_ratio"] = med[f"{k}_decode_long_null"] / (med[f"{k}_index_single"] + med[f"{k}_decode_single"])
+        # what building the tables adds to a decode: per record and per GiB
+        walk = med[f"{k}_decode_long_null"] - med[f"{k}_decode_long_table"]
+        res[f"{k}_null_walk_us_per_record"] = 1e3 * walk / dev[k]["count"]
+        res[f"{k}_null_walk_ms_per_gib"] = walk * (1 << 30) / n
 line = json.dumps(res)
 print(line)
 if tag:
