@@ -469,6 +469,103 @@ int snappy_frame_uncompressed_length(const uint8_t *in, size_t n, uint64_t *len)
 int snappy_compress_file_framed(FILE *file_input, unsigned long long input_size, FILE *file_compressed);
 int snappy_decompress_file_framed(FILE *file_input, FILE *file_decompressed);
 
+/* ---- Hadoop and snappy-java container streams ---------------------------- */
+/* The two length-prefixed containers most Snappy files on disk are in: the
+ * .snappy files of Hadoop's SnappyCodec (Hive, Spark) and the streams of
+ * snappy-java's SnappyOutputStream (Spark shuffle blocks, Kafka message sets).
+ * Big-endian 32-bit lengths in front of raw Snappy streams; no CRC, no chunk
+ * types.  Neither is the framing format above.
+ *
+ * SNAPPY_AMD_CONTAINER_HADOOP: a sequence of blocks.  A block is BE32 raw_len,
+ * then chunks BE32 comp_len | raw stream of comp_len bytes until the chunks'
+ * decoded lengths add up to raw_len; raw_len 0 is a block without chunks.  No
+ * file header, no trailer: 0 bytes are a valid empty stream.
+ * SNAPPY_AMD_CONTAINER_XERIAL: the 16-byte header 82 53 4e 41 50 50 59 00, BE32
+ * version, BE32 compatible_version (this library writes 1 and 1), then chunks
+ * BE32 comp_len | raw stream.  The header may stand again at any chunk
+ * boundary (concatenated streams): its first four bytes mark it.
+ *
+ * The compressor cuts the input into pieces of `block` bytes (0: the format's
+ * default, 131,072 for Hadoop, 32,768 for snappy-java; at most 2^30), each
+ * piece one chunk whose payload is exactly the bytes of snappy_compress() on
+ * the piece (the record of compress_long_records_device); in Hadoop each chunk
+ * is one block.  The output is a pure function of (input, block, format, flags).
+ *
+ * Chunk tables: two arrays of (offset, length) u64 pairs with one pair per
+ * chunk -- d_comp_off_len the payloads' places in the container, d_out_off_len
+ * their places in the decoded bytes -- the very arguments of
+ * snappy_amd_decompress_long_records_device.
+ *
+ * Errors of the walks (container_index_device, the host walk, decode without
+ * tables), the first failure in stream order:
+ *   ERR_TRUNCATED    fewer than 4 bytes where a length stands, a chunk that runs
+ *                    past the end, a snappy-java header cut short, a Hadoop
+ *                    stream that ends inside a block
+ *   ERR_HEADER       comp_len 0, a preamble that does not end inside the chunk's
+ *                    first five bytes, an empty or wrongly begun snappy-java stream
+ *   ERR_UNSUPPORTED  a chunk that declares more than 2^30 bytes,
+ *                    compatible_version above 1 (version is not checked)
+ *   ERR_OVERRUN      Hadoop: a chunk that declares more than its block has left
+ * The decoders run in two stages: the walk (or the check of the caller's
+ * tables against clen) reports its first failure, then ERR_CAPACITY, before
+ * anything is decoded; then the chunks are decoded as one long-record batch and
+ * the first failing chunk's status is returned with that call's meanings
+ * (ERR_OFFSET: a copy reached before its chunk's first byte; ERR_HEADER: a
+ * preamble that is not the table's length). */
+#define SNAPPY_AMD_CONTAINER_HADOOP 0
+#define SNAPPY_AMD_CONTAINER_XERIAL 1
+#define SNAPPY_AMD_CONTAINER_NO_HEADER 1u /* snappy-java: this buffer continues a stream (no effect in Hadoop) */
+
+/* Capacity d_out must have for compress_container_device: the stream header,
+ * 8 (Hadoop) or 4 bytes per chunk and snappy_amd_max_long_records_output(n,
+ * ceil(n / block)).  0 for an unknown format or a block above 2^30. */
+size_t snappy_amd_max_container_output(size_t n, uint32_t block, int format);
+/* Compress d_in[0..n) into one container.  d_comp_off_len / d_out_off_len
+ * (chunks_cap pairs each; either may be NULL) get the chunk tables, *nchunks
+ * ceil(n / block), *out_len the container's bytes.  n == 0 writes 0 bytes in
+ * Hadoop and the header alone in snappy-java.  Checked before anything is
+ * written: an unknown format, flag or block SNAPPY_AMD_ERR_ARG; out_cap below
+ * snappy_amd_max_container_output, or (a table given) chunks_cap below
+ * ceil(n / block), SNAPPY_AMD_ERR_CAPACITY.  The payloads are compressed into context scratch of
+ * snappy_amd_max_long_records_output(n, chunks) bytes by the long-record call
+ * and moved between their headers by one more pass.  No byte of d_out at or
+ * past *out_len is written. */
+int snappy_amd_compress_container_device(snappy_amd_ctx *ctx, const void *d_in, size_t n, uint32_t block, int format,
+                                         uint32_t flags, void *d_out, size_t out_cap, uint64_t *d_comp_off_len,
+                                         uint64_t *d_out_off_len, size_t chunks_cap, size_t *nchunks, size_t *out_len);
+/* Walk a container in HBM: the chunk tables (room for max_chunks pairs each),
+ * *nchunks and *n_out, the decoded bytes.  One wave follows the headers, one
+ * dependent step per chunk.  A walk failure comes first; more chunks than
+ * max_chunks is SNAPPY_AMD_ERR_CAPACITY, with *nchunks the pairs needed. */
+int snappy_amd_container_index_device(snappy_amd_ctx *ctx, const void *d_cont, size_t clen, int format,
+                                      uint64_t *d_comp_off_len, uint64_t *d_out_off_len, size_t max_chunks,
+                                      size_t *nchunks, size_t *n_out);
+/* Decode a container into d_out (cap bytes); *n_out = decoded bytes.  With both
+ * tables NULL the call walks the container itself (nchunks is not read).  With
+ * tables, every pair is checked against clen (a payload outside the container
+ * ERR_TRUNCATED, an empty one ERR_HEADER, a length above 2^30 ERR_UNSUPPORTED),
+ * *n_out is the end of the last output range, and that the tables are complete
+ * is the caller's word. */
+int snappy_amd_decompress_container_device(snappy_amd_ctx *ctx, const void *d_cont, size_t clen, int format,
+                                           const uint64_t *d_comp_off_len, const uint64_t *d_out_off_len,
+                                           size_t nchunks, void *d_out, size_t cap, size_t *n_out);
+/* Host memory: out must hold snappy_amd_max_container_output(n, block, format).
+ * Inputs of more than 64 MiB go piece by piece, a piece a multiple of the block
+ * (the decoders cut at the last whole chunk and carry the rest, Hadoop's open
+ * block included); SNAPPY_AMD_CONTAINER_PIECE_KB sets another piece size (the
+ * bytes written do not depend on it).  The decoders walk on the host, by the
+ * same rule as container_index_device, and upload the tables. */
+int snappy_compress_container_buffer(const uint8_t *in, size_t n, uint32_t block, int format, uint8_t *out, size_t cap,
+                                     size_t *out_len);
+int snappy_decompress_container_buffer(const uint8_t *in, size_t n, int format, uint8_t *out, size_t cap,
+                                       size_t *out_len);
+/* Decoded bytes of a container: the walk on the host (no kernel). */
+int snappy_container_uncompressed_length(const uint8_t *in, size_t n, int format, uint64_t *len);
+/* FILE* forms: file_input from its current position to EOF. */
+int snappy_compress_file_container(FILE *file_input, unsigned long long input_size, uint32_t block, int format,
+                                   FILE *file_compressed);
+int snappy_decompress_file_container(FILE *file_input, int format, FILE *file_decompressed);
+
 /* Kernel timing of the last compress/decompress call, measured with HIP
  * events on the launch stream: K1 (block compress), K3 (scan + gather),
  * K4 (block decode), milliseconds. */

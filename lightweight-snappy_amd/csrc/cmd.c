@@ -9,6 +9,9 @@
  * -f (an addition): with -c write, with -d read the Snappy framing format
  * (framing_format.txt of google/snappy), the file format of other Snappy
  * tools; not with -b or -i.
+ * -F hadoop|xerial (an addition): with -c write, with -d read the container of
+ * Hadoop's SnappyCodec (.snappy files) or of snappy-java's SnappyOutputStream;
+ * not with -b, -i or -f.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -28,7 +31,8 @@ static void usage(void)
             "-d decompress (MI355X)\n"
             "-r print results\n"
             "-i -c: also write outfile.idx (block index); -d: use infile.idx\n"
-            "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n");
+            "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n"
+            "-F hadoop|xerial with -c or -d: the Hadoop SnappyCodec / snappy-java container\n");
     exit(EXIT_FAILURE);
 }
 
@@ -53,19 +57,22 @@ static unsigned long long file_size(FILE *f)
 int main(int argc, char *argv[])
 {
     enum { M_COMPRESS, M_BST, M_DECOMPRESS } mode = M_COMPRESS;
-    int show = 0, indexed = 0, framed = 0, opt;
+    int show = 0, indexed = 0, framed = 0, container = -1, opt;
     if (argc < 4) usage();
-    while ((opt = getopt(argc, argv, "cbdrif")) != -1) {
+    while ((opt = getopt(argc, argv, "cbdrifF:")) != -1) {
         if (opt == 'c') mode = M_COMPRESS;
         else if (opt == 'b') mode = M_BST;
         else if (opt == 'd') mode = M_DECOMPRESS;
         else if (opt == 'r') show = 1;
         else if (opt == 'i') indexed = 1;
         else if (opt == 'f') framed = 1;
+        else if (opt == 'F' && strcmp(optarg, "hadoop") == 0) container = SNAPPY_AMD_CONTAINER_HADOOP;
+        else if (opt == 'F' && strcmp(optarg, "xerial") == 0) container = SNAPPY_AMD_CONTAINER_XERIAL;
         else usage();
     }
     if (indexed && mode == M_BST) usage();  /* -b writes no block index */
     if (framed && (indexed || mode == M_BST)) usage();  /* a framed stream has its chunk headers; -b is unframed */
+    if (container >= 0 && (framed || indexed || mode == M_BST)) usage();  /* one file format at a time */
     const char *in_name = argv[argc - 2], *out_name = argv[argc - 1];
     FILE *in = open_or_die(in_name, "rb");
     FILE *out = open_or_die(out_name, "wb");
@@ -80,7 +87,10 @@ int main(int argc, char *argv[])
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     int rc = 0;
-    if (framed) {
+    if (container >= 0) {
+        rc = mode == M_COMPRESS ? snappy_compress_file_container(in, in_size, 0, container, out)
+                                : snappy_decompress_file_container(in, container, out);
+    } else if (framed) {
         rc = mode == M_COMPRESS ? snappy_compress_file_framed(in, in_size, out) : snappy_decompress_file_framed(in, out);
     } else if (mode == M_COMPRESS && idx) {
         rc = snappy_compress_file_indexed(in, in_size, out, idx);

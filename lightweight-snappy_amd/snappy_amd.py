@@ -38,6 +38,11 @@ ERR_INDEX = -11
 ERR_CHECKSUM = -12
 FRAME_NO_IDENTIFIER = 1  # compress_frame_*: this buffer continues a framed stream
 FRAME_IDENTIFIER = bytes.fromhex("ff060000734e61507059")
+CONTAINER_HADOOP = 0  # Hadoop SnappyCodec blocks (.snappy files)
+CONTAINER_XERIAL = 1  # snappy-java SnappyOutputStream chunks
+CONTAINER_NO_HEADER = 1  # compress_container_*: this buffer continues a snappy-java stream
+CONTAINER_HEADER = bytes.fromhex("82534e41505059000000000100000001")
+CONTAINER_BLOCK = {CONTAINER_HADOOP: 131072, CONTAINER_XERIAL: 32768}  # the pieces of block=0
 IDX_MAGIC = 0x3158444941504E53  # b"SNPAIDX1" as a little-endian u64
 
 BLOCK = 65536
@@ -171,6 +176,26 @@ _SIGS = {
                                                              _c.c_void_p, _c.c_void_p, _c.c_int]),
     "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
     "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
+    # Hadoop / snappy-java containers
+    "snappy_amd_max_container_output": (_c.c_size_t, [_c.c_size_t, _c.c_uint32, _c.c_int]),
+    "snappy_amd_compress_container_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_int,
+                                                        _c.c_uint32, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                        _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t),
+                                                        _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_container_index_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p,
+                                                     _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t),
+                                                     _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_decompress_container_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                                          _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                          _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "snappy_compress_container_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_int, _c.c_void_p,
+                                                    _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "snappy_decompress_container_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                                      _c.POINTER(_c.c_size_t)]),
+    "snappy_container_uncompressed_length": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int,
+                                                        _c.POINTER(_c.c_uint64)]),
+    "snappy_compress_file_container": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_uint32, _c.c_int, _c.c_void_p]),
+    "snappy_decompress_file_container": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p]),
 }
 # the reference Buffer cursor helpers, in libsnappy_amd_compat.so (Buffer* is a
 # struct of two pointers and a u32)
@@ -366,6 +391,53 @@ def decompress_frame(data, cap: Optional[int] = None) -> bytes:
     out = ctypes.create_string_buffer(max(cap, 1))
     got = ctypes.c_size_t(0)
     _check(lib().snappy_decompress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "decompress_frame")
+    return out.raw[: got.value]
+
+
+def container_format(format) -> int:
+    """CONTAINER_HADOOP / CONTAINER_XERIAL from the constant or its name ("hadoop", "xerial")."""
+    if isinstance(format, str):
+        try:
+            return {"hadoop": CONTAINER_HADOOP, "xerial": CONTAINER_XERIAL}[format]
+        except KeyError:
+            raise SnappyError(ERR_ARG, f"container format {format!r}") from None
+    return int(format)
+
+
+def max_container_output(n: int, block: int, format) -> int:
+    return lib().snappy_amd_max_container_output(n, block, container_format(format))
+
+
+def compress_container(data, format, block: int = 0) -> bytes:
+    """data as a Hadoop SnappyCodec stream or a snappy-java SnappyOutputStream
+    stream: one chunk per `block` input bytes (0: the format's default)."""
+    fmt = container_format(format)
+    p, n, keep = _buf(data)
+    cap = max_container_output(n, block, fmt)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_compress_container_buffer(p, n, block, fmt, out, cap, ctypes.byref(got)), "compress_container")
+    return out.raw[: got.value]
+
+
+def container_uncompressed_length(data, format) -> int:
+    """Decoded bytes of a container stream (the header walk on the host, no GPU)."""
+    p, n, keep = _buf(data)
+    v = ctypes.c_uint64(0)
+    _check(lib().snappy_container_uncompressed_length(p, n, container_format(format), ctypes.byref(v)),
+           "container_uncompressed_length")
+    return v.value
+
+
+def decompress_container(data, format, cap: Optional[int] = None) -> bytes:
+    """Decode a Hadoop or snappy-java container stream of any writer."""
+    fmt = container_format(format)
+    p, n, keep = _buf(data)
+    if cap is None:
+        cap = container_uncompressed_length(data, fmt)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_decompress_container_buffer(p, n, fmt, out, cap, ctypes.byref(got)), "decompress_container")
     return out.raw[: got.value]
 
 
@@ -638,6 +710,91 @@ class Codec:
                                                         ctypes.c_void_p(chunks.data_ptr()), chunks.numel() - 1,
                                                         ctypes.c_void_p(out.data_ptr()), n, ctypes.byref(got)),
                "decompress_frame_device")
+        return out[: got.value]
+
+    # Hadoop / snappy-java containers -------------------------------------------
+    def compress_container_tensor(self, x, format, block: int = 0, flags: int = 0, out=None, tables: bool = True):
+        """x: contiguous uint8 CUDA tensor -> (container tensor, payload pairs,
+        output pairs): the chunk tables are int64 tensors of (offset, length)
+        pairs, one per chunk (None, None with tables=False).  `out` (a uint8 CUDA
+        tensor, any alignment) takes the container; its size is the capacity."""
+        assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        fmt = container_format(format)
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(max_container_output(n, block, fmt), 1), dtype=torch.uint8, device=x.device)
+        b = block or CONTAINER_BLOCK.get(fmt, 1)
+        chunks = (n + b - 1) // b
+        comp = outp = None
+        if tables:
+            comp = torch.empty(2 * max(chunks, 1), dtype=torch.int64, device=x.device)
+            outp = torch.empty(2 * max(chunks, 1), dtype=torch.int64, device=x.device)
+        nch, got = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_compress_container_device(
+            self._h, ctypes.c_void_p(x.data_ptr()), n, block, fmt, flags, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(comp.data_ptr() if tables else 0), ctypes.c_void_p(outp.data_ptr() if tables else 0),
+            chunks, ctypes.byref(nch), ctypes.byref(got)), "compress_container_device")
+        if tables:
+            comp, outp = comp[: 2 * nch.value], outp[: 2 * nch.value]
+        return out[: got.value], comp, outp
+
+    def container_index_tensor(self, cont, format, max_chunks: Optional[int] = None, clen: Optional[int] = None):
+        """Chunk tables of a container in HBM -> (decoded bytes, payload pairs,
+        output pairs).  A container holds at most one chunk per 5 bytes, which
+        bounds the tables when max_chunks is not given.  clen: walk only the
+        first clen bytes of cont."""
+        assert cont.is_cuda and cont.dtype == torch.uint8 and cont.is_contiguous()
+        if clen is None:
+            clen = cont.numel()
+        if max_chunks is None:
+            max_chunks = clen // 5 + 1
+        comp = torch.empty(2 * max(max_chunks, 1), dtype=torch.int64, device=cont.device)
+        outp = torch.empty(2 * max(max_chunks, 1), dtype=torch.int64, device=cont.device)
+        nch, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_container_index_device(self._h, ctypes.c_void_p(cont.data_ptr()), clen,
+                                                       container_format(format), ctypes.c_void_p(comp.data_ptr()),
+                                                       ctypes.c_void_p(outp.data_ptr()), max_chunks, ctypes.byref(nch),
+                                                       ctypes.byref(n)), "container_index_device")
+        return n.value, comp[: 2 * nch.value], outp[: 2 * nch.value]
+
+    def decompress_container_tensor(self, cont, format, comp=None, outp=None, cap: Optional[int] = None, out=None,
+                                    clen: Optional[int] = None):
+        """Decode a container in HBM.  comp / outp: the chunk tables of
+        compress_container_tensor or container_index_tensor, or both None: the
+        call walks the container itself.  cap: the room for decoded bytes (the
+        tables' extent, or the host does not know: pass it or `out`)."""
+        assert cont.is_cuda and cont.dtype == torch.uint8 and cont.is_contiguous()
+        assert (comp is None) == (outp is None)
+        fmt = container_format(format)
+        if clen is None:
+            clen = cont.numel()
+        if out is not None:
+            cap = out.numel() if cap is None else cap
+        elif cap is None:
+            if comp is None:
+                # a walk that stores nothing: ERR_CAPACITY only says that it found chunks
+                n = ctypes.c_size_t(0)
+                self._bind_stream()
+                rc = lib().snappy_amd_container_index_device(self._h, ctypes.c_void_p(cont.data_ptr()), clen, fmt,
+                                                             ctypes.c_void_p(0), ctypes.c_void_p(0), 0, None,
+                                                             ctypes.byref(n))
+                if rc != ERR_CAPACITY:
+                    _check(rc, "container_index_device")
+                cap = n.value
+            else:
+                cap = int((outp[0::2] + outp[1::2]).max().item()) if outp.numel() else 0
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=cont.device)
+        nch = 0 if comp is None else comp.numel() // 2
+        got = ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_decompress_container_device(
+            self._h, ctypes.c_void_p(cont.data_ptr()), clen, fmt,
+            ctypes.c_void_p(comp.data_ptr() if comp is not None else 0),
+            ctypes.c_void_p(outp.data_ptr() if outp is not None else 0), nch, ctypes.c_void_p(out.data_ptr()), cap,
+            ctypes.byref(got)), "decompress_container_device")
         return out[: got.value]
 
     # record batches ------------------------------------------------------------

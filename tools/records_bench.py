@@ -15,15 +15,25 @@ and the long-record calls:
   f  256 KiB records                >  vs  the SINGLE call on the same N bytes
   g  a seeded log-uniform mix of 64 B .. 4 MiB records  /
 
+and the container calls, each format at its default block:
+
+  h  Hadoop SnappyCodec, 131,072-byte pieces       \  vs  the long-record calls on the
+  x  snappy-java SnappyOutputStream, 32,768-byte    /  same pieces / the same chunks
+
 The STREAMS calls are the yardstick of a and b (their min..max is the spread a
 difference has to exceed); c and d have no fixed-layout counterpart.  The
 yardstick of e, f and g is the SINGLE call in the same round: its compress for the
 long compress, its decode for the long decode with compress's tables, and
 snappy_amd_index_device + its decode for the long decode that builds the tables
 (NULL).  The walk a NULL decode adds is also reported per record and per GiB.
+The yardsticks of h and x, in the same round: compress_long_records_device on the
+same pieces (no block tables asked for, as the container call asks for none) for
+the container compress; decompress_long_records_device with NULL block tables on
+the container's own chunk tables for the container decode with tables given.
+container_index_device alone is reported per chunk.
 
 Prints one JSON line and writes it to profiles/<tag>.json when a tag is given:
-    python tools/records_bench.py [n_bytes] [reps] [tag] [legs, default abcdefg]
+    python tools/records_bench.py [n_bytes] [reps] [tag] [legs, default abcdefg; hx on request]
 Run under rocprofv3 --kernel-trace --stats (a run of its own) for per-kernel times."""
 import json
 import os
@@ -42,6 +52,7 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 11
 tag = sys.argv[3] if len(sys.argv) > 3 else ""
 which = sys.argv[4] if len(sys.argv) > 4 else "abcdefg"
 LONG = "efg"
+CONTAINER = {"h": snappy_amd.CONTAINER_HADOOP, "x": snappy_amd.CONTAINER_XERIAL}
 
 host = np.empty(n, dtype=np.uint8)
 datagen.fill(host, "T", 1234, threads=16)
@@ -69,7 +80,9 @@ def log_uniform(seed=1234, hi=65536):
 
 
 legs = {"a": uniform(32768), "b": uniform(65536), "c": log_uniform(), "d": uniform(4096),
-        "e": uniform(1 << 20), "f": uniform(256 << 10), "g": log_uniform(4321, 4 << 20)}
+        "e": uniform(1 << 20), "f": uniform(256 << 10), "g": log_uniform(4321, 4 << 20),
+        "h": uniform(snappy_amd.CONTAINER_BLOCK[snappy_amd.CONTAINER_HADOOP]),
+        "x": uniform(snappy_amd.CONTAINER_BLOCK[snappy_amd.CONTAINER_XERIAL])}
 legs = {k: v[v[:, 1] > 0] for k, v in legs.items() if k in which}
 max_count = max(len(v) for v in legs.values())
 out = torch.empty(max(snappy_amd.max_records_output(n, max_count), snappy_amd.max_long_records_output(n, max_count),
@@ -82,6 +95,12 @@ for k, v in legs.items():
               "col": torch.empty(2 * len(v), dtype=torch.int64, device="cuda"), "clen": 0}
     if k in LONG:
         dev[k]["index"] = torch.empty(snappy_amd.max_records_index(n, len(v)), dtype=torch.int64, device="cuda")
+    if k in CONTAINER:
+        dev[k]["comp"] = torch.empty(2 * len(v), dtype=torch.int64, device="cuda")
+        dev[k]["outp"] = torch.empty(2 * len(v), dtype=torch.int64, device="cuda")
+        dev[k]["cont_len"] = 0
+cont = torch.empty(max([snappy_amd.max_container_output(n, 0, f) for k, f in CONTAINER.items() if k in legs] + [1]),
+                   dtype=torch.uint8, device="cuda")
 units = (n + snappy_amd.BLOCK - 1) // snappy_amd.BLOCK
 state = {"single_offs": torch.empty(units + 1, dtype=torch.int64, device="cuda"),
          "single_index": torch.empty(units + 1, dtype=torch.int64, device="cuda")}
@@ -119,6 +138,71 @@ def decode_long(k, with_table):
         h, vp(out.data_ptr()), d["clen"], vp(d["col"].data_ptr()), d["count"], vp(back.data_ptr()), n,
         vp(d["ol"].data_ptr()), vp(d["index"].data_ptr()) if with_table else None, None, 1),
         "decompress_long_records_device")
+
+
+def compress_container(k):
+    d = dev[k]
+    nch, got = ct.c_size_t(0), ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_compress_container_device(
+        h, vp(x.data_ptr()), n, 0, CONTAINER[k], 0, vp(cont.data_ptr()), cont.numel(), vp(d["comp"].data_ptr()),
+        vp(d["outp"].data_ptr()), d["count"], ct.byref(nch), ct.byref(got)), "compress_container_device")
+    assert nch.value == d["count"]
+    d["cont_len"] = got.value
+
+
+def compress_long_pieces(k):
+    d = dev[k]
+    got = ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_compress_long_records_device(
+        h, vp(x.data_ptr()), n, vp(d["ol"].data_ptr()), d["count"], vp(out.data_ptr()), out.numel(),
+        vp(d["offs"].data_ptr()), None, 0, None, ct.byref(got)), "compress_long_records_device")
+    d["clen"] = got.value
+
+
+def decode_container(k):
+    d = dev[k]
+    got = ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_decompress_container_device(
+        h, vp(cont.data_ptr()), d["cont_len"], CONTAINER[k], vp(d["comp"].data_ptr()), vp(d["outp"].data_ptr()),
+        d["count"], vp(back.data_ptr()), n, ct.byref(got)), "decompress_container_device")
+    assert got.value == n
+
+
+def decode_long_chunks(k):
+    d = dev[k]
+    snappy_amd._check(lib.snappy_amd_decompress_long_records_device(
+        h, vp(cont.data_ptr()), d["cont_len"], vp(d["comp"].data_ptr()), d["count"], vp(back.data_ptr()), n,
+        vp(d["outp"].data_ptr()), None, None, 1), "decompress_long_records_device")
+
+
+def index_container(k):
+    d = dev[k]
+    nch, got = ct.c_size_t(0), ct.c_size_t(0)
+    snappy_amd._check(lib.snappy_amd_container_index_device(
+        h, vp(cont.data_ptr()), d["cont_len"], CONTAINER[k], vp(d["icomp"].data_ptr()), vp(d["ioutp"].data_ptr()),
+        d["count"], ct.byref(nch), ct.byref(got)), "container_index_device")
+    assert (nch.value, got.value) == (d["count"], n)
+
+
+def container_round(k, r):
+    """one round of a container leg and of its yardsticks -> {name: ms}"""
+    d = dev[k]
+    if "icomp" not in d:
+        d["icomp"], d["ioutp"] = torch.empty_like(d["comp"]), torch.empty_like(d["outp"])
+    t = {"compress_container": timed(compress_container, k), "compress_long": timed(compress_long_pieces, k)}
+    for name, fn in (("decode_container_table", decode_container), ("decode_long_null", decode_long_chunks)):
+        if r == 1:
+            back.zero_()
+        t[name] = timed(fn, k)
+        if r == 1:
+            assert torch.equal(back, x), f"leg {k}: {name} round trip failed"
+    t["index_container"] = timed(index_container, k)
+    if r == 1:
+        assert torch.equal(d["icomp"], d["comp"]) and torch.equal(d["ioutp"], d["outp"])
+        # the container is the long-record payload with a header in front of every record
+        hdr = 8 if k == "h" else 4
+        assert d["cont_len"] == d["clen"] + hdr * d["count"] + (16 if k == "x" else 0)
+    return t
 
 
 def compress_single():
@@ -180,8 +264,8 @@ ms = {}
 with torch.cuda.stream(stream):
     for r in range(reps + 2):  # two warm-up rounds (code objects, scratch growth)
         for k in legs:
-            if k in LONG:
-                t = long_round(k, r)
+            if k in LONG or k in CONTAINER:
+                t = long_round(k, r) if k in LONG else container_round(k, r)
                 if r >= 2:
                     for name, v in t.items():
                         ms.setdefault(f"{k}_{name}", []).append(v)
@@ -216,7 +300,8 @@ held = codec.device_bytes()
 codec.close()
 med = {k: median(v) for k, v in ms.items()}
 res = {"n": n, "reps": reps, "records": {k: dev[k]["count"] for k in legs},
-       "compressed_bytes": {k: dev[k]["clen"] for k in legs}, "device_bytes": held, "median_ms": med,
+       "compressed_bytes": {k: dev[k]["clen"] for k in legs},
+       "container_bytes": {k: dev[k]["cont_len"] for k in legs if k in CONTAINER}, "device_bytes": held, "median_ms": med,
        "min_max_ms": {k: [min(v), max(v)] for k, v in ms.items()}}
 for k in legs:
     if k in "ab":
@@ -230,6 +315,12 @@ for k in legs:
         walk = med[f"{k}_decode_long_null"] - med[f"{k}_decode_long_table"]
         res[f"{k}_null_walk_us_per_record"] = 1e3 * walk / dev[k]["count"]
         res[f"{k}_null_walk_ms_per_gib"] = walk * (1 << 30) / n
+    if k in CONTAINER:
+        res[f"{k}_compress_ratio"] = med[f"{k}_compress_container"] / med[f"{k}_compress_long"]
+        res[f"{k}_compress_extra_ms"] = med[f"{k}_compress_container"] - med[f"{k}_compress_long"]
+        res[f"{k}_decode_table_ratio"] = med[f"{k}_decode_container_table"] / med[f"{k}_decode_long_null"]
+        res[f"{k}_decode_table_extra_ms"] = med[f"{k}_decode_container_table"] - med[f"{k}_decode_long_null"]
+        res[f"{k}_index_us_per_chunk"] = 1e3 * med[f"{k}_index_container"] / dev[k]["count"]
 line = json.dumps(res)
 print(line)
 if tag:
