@@ -390,6 +390,84 @@ int snappy_amd_decompress_long_records_device(snappy_amd_ctx *ctx, const void *d
                                               size_t out_bytes, const uint64_t *d_out_off_len, const uint64_t *d_index,
                                               int32_t *d_status, int sync);
 
+/* ---- range decode: bytes [start, start + length) through the block index --- */
+/* Random access into a stream whose block index is known (compress_device's
+ * d_offsets, the sidecar file, index_device): only the blocks a range touches are
+ * decoded, and only their compressed bytes need to be in HBM.
+ *
+ * d_comp[0, comp_bytes) holds the stream's bytes [comp_origin, comp_origin +
+ * comp_bytes): the resident window (comp_origin = 0 and the whole stream is the
+ * plain case).  d_offsets is always the stream's full index, units + 1 entries
+ * with stream-relative values in the format of snappy_amd_index_device; n, chunk
+ * and layout as in decompress_device.  SINGLE: blocks of 65,536 bytes; the
+ * preamble is checked only when block 0 is decoded, and must equal n.  STREAMS:
+ * units of `chunk` bytes, each with its own preamble.
+ *
+ * Range i (host memory) writes the stream's decoded bytes [start, start + length)
+ * to d_out[out_offset, out_offset + length).  Ranges may overlap in the stream;
+ * overlapping output ranges are the caller's error; length == 0 is OK and touches
+ * nothing.  The host plans (csrc/snappy_ranges.h): one decode unit per (range,
+ * block) pair -- a block that several ranges share is decoded once per range.  A
+ * unit that lies wholly inside its range decodes straight into d_out; an edge
+ * unit decodes its whole block into a 65,536-byte staging slot in context scratch
+ * and a second kernel copies the wanted part out.  At most 1,024 slots (64 MiB,
+ * SNAPPY_RANGES_SLOT_CAP) are held: more edge units run in successive launches
+ * that reuse them, so scratch stays within 64 MiB plus 32 bytes per planned unit
+ * and 8 per range.  The call needs no read-back to size its launches: with sync =
+ * 0 it returns once the work is queued.  A range decodes fastest when out_offset
+ * and start agree mod 16 (16-byte stores).
+ *
+ * d_status (count i32, device; may be NULL) gets every range's status; a refused
+ * or failing range does not disturb its neighbours; sync = 1 returns the first
+ * failing range's status.  In this order, the first three before any byte of the
+ * range is loaded or stored:
+ *   ERR_ARG        the range leaves [0, n)
+ *   ERR_CAPACITY   the output range leaves [0, out_bytes)
+ *   ERR_TRUNCATED  one of the range's units has compressed bytes [entry[u],
+ *                  entry[u+1]) that are not inside the resident window; if entry
+ *                  u+1 carries skip bits, the bytes up to the end of the element
+ *                  that straddles out count too
+ *   ERR_DEPENDENT  SINGLE only: a unit of the range resumes a copy, or copies from
+ *                  before its own block -- what pass 1 of the whole-stream decode
+ *                  defers.  This call has no second pass: decode the stream whole.
+ *   ERR_OFFSET     STREAMS: a copy reaches before its unit, as in decompress_device
+ *   ERR_INDEX, ERR_HEADER, element errors: as the block decode reports them for
+ *                  the units decoded; the lowest failing unit of the range wins.  A
+ *                  corrupt block outside the ranges is never seen.
+ * No byte of d_out outside the ranges is written (a failing range may leave part
+ * of its own output range written); no read leaves the resident window, except
+ * within the aligned dword that holds its first byte.
+ *
+ * What success proves: each decoded block's element chain ran from its entry
+ * exactly to the next entry.  Unlike the whole-stream decode it does not prove
+ * that the first entry of a range is a true element boundary -- the induction
+ * from block 0 is missing -- so that entry is taken on the caller's word. */
+#define SNAPPY_AMD_ERR_DEPENDENT (-13) /* a block of the range needs bytes of an earlier block */
+
+typedef struct { uint64_t start, length, out_offset; } snappy_amd_range; /* host memory */
+
+int snappy_amd_decompress_ranges_device(snappy_amd_ctx *ctx, const void *d_comp, uint64_t comp_origin,
+                                        size_t comp_bytes, const uint64_t *d_offsets, size_t n, uint32_t chunk,
+                                        int layout, const snappy_amd_range *ranges, size_t count, void *d_out,
+                                        size_t out_bytes, int32_t *d_status, int sync);
+
+/* Host forms: bytes [start, start + length) of snappy_decompress_buffer's output,
+ * always exactly that slice.  idx = the sidecar file's bytes (or stream); NULL:
+ * no sidecar -- the whole stream is uploaded and indexed on the GPU.  With a
+ * sidecar: it is checked as in snappy_decompress_file_indexed, the stream's
+ * preamble (its first bytes, at most 10) must equal the sidecar's N
+ * (SNAPPY_AMD_ERR_INDEX), only the compressed bytes of the blocks the range
+ * touches are read (fseeko in the FILE* form: a file_input that cannot seek is
+ * SNAPPY_AMD_ERR_UNSUPPORTED) and uploaded, and only `length` bytes come back.  A
+ * range that leaves [0, N) is SNAPPY_AMD_ERR_ARG.  Foreign streams whose range
+ * is not self-contained (ERR_DEPENDENT, or skip bits on the range's first entry
+ * or on the entry after its last block) are decoded whole and sliced; any other
+ * failure with a sidecar loads the whole stream and is judged as in
+ * snappy_decompress_file_indexed (ERR_INDEX: not this stream's index). */
+int snappy_decompress_range_buffer(const uint8_t *in, size_t n, const uint8_t *idx, size_t idx_bytes, uint64_t start,
+                                   size_t length, uint8_t *out, size_t cap, size_t *out_len);
+int snappy_decompress_file_range(FILE *file_input, FILE *idx, uint64_t start, uint64_t length, FILE *file_out);
+
 /* ---- Snappy framing format (framing_format.txt of google/snappy) -------- */
 /* The file format other Snappy tools exchange: the 10-byte stream identifier
  * ff 06 00 00 "sNaPpY", then chunks -- a type byte, a 24-bit little-endian

@@ -12,6 +12,11 @@
  * -F hadoop|xerial (an addition): with -c write, with -d read the container of
  * Hadoop's SnappyCodec (.snappy files) or of snappy-java's SnappyOutputStream;
  * not with -b, -i or -f.
+ * -R start:length (an addition): with -d write only the decoded bytes [start,
+ * start + length) of the stream.  With -i only the compressed bytes of the
+ * blocks the range touches are read from infile (which must be seekable);
+ * without -i the stream is read whole and indexed on the GPU.  Not with -c, -b,
+ * -f or -F.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -25,14 +30,15 @@
 static void usage(void)
 {
     fprintf(stderr,
-            "snappy [-c|-d|-b] [-r] [-i] [-f] [infile] [outfile]\n"
+            "snappy [-c|-d|-b] [-r] [-i] [-f] [-F format] [-R start:length] [infile] [outfile]\n"
             "-c compress (MI355X)\n"
             "-b compress with the BST matcher\n"
             "-d decompress (MI355X)\n"
             "-r print results\n"
             "-i -c: also write outfile.idx (block index); -d: use infile.idx\n"
             "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n"
-            "-F hadoop|xerial with -c or -d: the Hadoop SnappyCodec / snappy-java container\n");
+            "-F hadoop|xerial with -c or -d: the Hadoop SnappyCodec / snappy-java container\n"
+            "-R start:length with -d: only the decoded bytes [start, start + length) (-i: read only their blocks)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -57,10 +63,11 @@ static unsigned long long file_size(FILE *f)
 int main(int argc, char *argv[])
 {
     enum { M_COMPRESS, M_BST, M_DECOMPRESS } mode = M_COMPRESS;
-    int show = 0, indexed = 0, framed = 0, container = -1, opt;
+    int show = 0, indexed = 0, framed = 0, container = -1, ranged = 0, compress_flag = 0, opt;
+    unsigned long long r_start = 0, r_length = 0;
     if (argc < 4) usage();
-    while ((opt = getopt(argc, argv, "cbdrifF:")) != -1) {
-        if (opt == 'c') mode = M_COMPRESS;
+    while ((opt = getopt(argc, argv, "cbdrifF:R:")) != -1) {
+        if (opt == 'c') mode = M_COMPRESS, compress_flag = 1;
         else if (opt == 'b') mode = M_BST;
         else if (opt == 'd') mode = M_DECOMPRESS;
         else if (opt == 'r') show = 1;
@@ -68,11 +75,23 @@ int main(int argc, char *argv[])
         else if (opt == 'f') framed = 1;
         else if (opt == 'F' && strcmp(optarg, "hadoop") == 0) container = SNAPPY_AMD_CONTAINER_HADOOP;
         else if (opt == 'F' && strcmp(optarg, "xerial") == 0) container = SNAPPY_AMD_CONTAINER_XERIAL;
+        else if (opt == 'R') {
+            /* two unsigned decimal numbers around one colon, nothing else */
+            char *end = NULL;
+            errno = 0;
+            if (optarg[0] < '0' || optarg[0] > '9') usage();
+            r_start = strtoull(optarg, &end, 10);
+            if (errno || *end != ':' || end[1] < '0' || end[1] > '9') usage();
+            r_length = strtoull(end + 1, &end, 10);
+            if (errno || *end) usage();
+            ranged = 1;
+        }
         else usage();
     }
     if (indexed && mode == M_BST) usage();  /* -b writes no block index */
     if (framed && (indexed || mode == M_BST)) usage();  /* a framed stream has its chunk headers; -b is unframed */
     if (container >= 0 && (framed || indexed || mode == M_BST)) usage();  /* one file format at a time */
+    if (ranged && (mode != M_DECOMPRESS || compress_flag || framed || container >= 0)) usage();  /* -R: a raw stream's decode */
     const char *in_name = argv[argc - 2], *out_name = argv[argc - 1];
     FILE *in = open_or_die(in_name, "rb");
     FILE *out = open_or_die(out_name, "wb");
@@ -99,6 +118,9 @@ int main(int argc, char *argv[])
         rc = snappy_amd_last_status();
     } else if (mode == M_BST) {
         rc = snappy_compress_bst(in, in_size, out);
+    } else if (ranged) {
+        rc = snappy_decompress_file_range(in, idx, r_start, r_length, out);
+        if (rc != 0) fprintf(stderr, "snappy_decompress_file_range: error %d\n", rc);
     } else if (idx) {
         rc = snappy_decompress_file_indexed(in, idx, out);
     } else {

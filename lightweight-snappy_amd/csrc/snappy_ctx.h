@@ -45,6 +45,10 @@ struct snappy_amd_ctx {
     // record batches (snappy_records.hip): the plan pass's tables and result words
     // (the records' token scratch is `tokens`, their sizes and counts `sizes` / `ntok`)
     uint8_t *r_meta = nullptr; size_t r_meta_cap = 0;
+    // range decode (snappy_ranges.hip): the host's plan in pinned memory and the event
+    // of its last upload (the device copy is r_meta, the staging slots f_scr)
+    uint8_t *h_plan = nullptr; size_t h_plan_cap = 0;
+    hipEvent_t plan_ev = nullptr;
     bool timing = false;
     bool serial_index = false;  // SNAPPY_AMD_OPT_SERIAL_INDEX
     uint32_t k1r_extra_lds = 0; // SNAPPY_AMD_OPT_K1R_EXTRA_LDS

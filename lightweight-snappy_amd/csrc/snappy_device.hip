@@ -147,6 +147,8 @@ void snappy_amd_destroy(snappy_amd_ctx *c)
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->h_total) (void)hipHostFree(c->h_total);
     if (c->h_status) (void)hipHostFree(c->h_status);
+    if (c->h_plan) (void)hipHostFree(c->h_plan);
+    if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
     for (int i = 0; i < 5; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "snappy_ranges.h"
+
 #define SNAPPY_LAYOUT_SINGLE 0
 #define SNAPPY_LAYOUT_STREAMS 1
 #define SNAPPY_BLOCK 65536u
@@ -25,6 +27,7 @@
 #define SNAPPY_ST_UNSUPPORTED (-9)
 #define SNAPPY_ST_TIMEOUT (-10)   // K4 pass 2: a unit waited too long for an earlier one
 #define SNAPPY_ST_INDEX (-11)     // K4 (SINGLE): the unit's element chain does not end at the next index entry
+#define SNAPPY_ST_DEPENDENT (-13) // range decode (SINGLE): the unit needs bytes of an earlier block; no pass 2 there
 #define SNAPPY_ST_DEFER 2         // K4 pass 1: the unit copies from earlier units (pass 2 decodes it;
                                   // meanwhile its status is DEFER + output bytes already in HBM)
 
@@ -152,6 +155,24 @@ struct K4LongArgs {
 // K4 pass 1 and pass 2 (grid x = units): k4_body with the SINGLE-layout arguments of the unit's record
 __global__ void kr4_decode_lunits(const K4LongArgs a);
 __global__ void kr4_back_lunits(const K4LongArgs a);
+
+// ---- range decode (snappy_ranges.hip): the planned units of snappy_ranges.h
+struct K4RangeArgs {
+    uintptr_t comp_at;              // the address of the stream's byte 0: d_comp - comp_origin (any alignment)
+    uint64_t win_end;               // comp_origin + comp_bytes: the end of the resident window, stream-relative
+    const uint64_t *offsets;        // the stream's full index
+    uint64_t n;
+    uint32_t unit, hdr_mode, allow_back;
+    uint32_t slot_cap;              // staging slots in use (edge k uses slot (k - 1) % slot_cap)
+    const snappy_range_unit *plan;  // the planned units
+    uint64_t first;                 // this launch's first planned unit
+    unsigned long long *keys;       // per range: ~0, < 256 refused before any load (-status), else the
+                                    // lowest failing unit: (unit + 1) << 8 | -status
+    uint8_t *slots;
+    uint8_t *out;
+};
+// K4 pass 1 over planned units [first, first + grid x), one wave each
+__global__ void kr4_decode_range_units(const K4RangeArgs a);
 
 #ifndef SNAPPY_K5_CHUNK
 #define SNAPPY_K5_CHUNK 16384

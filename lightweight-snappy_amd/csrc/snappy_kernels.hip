@@ -19,6 +19,10 @@
 //       kr4_back_lunits:   the same bodies, the K5 walk and K4 pass 2 over the blocks
 //                          of long records -- a unit is one block of one record
 //                          (snappy_long_records.hip holds the plan, the expansion and the launches)
+//   KG  kr4_decode_range_units: K4 pass 1 over the planned units of a range decode --
+//                          a unit is one block of the stream for one range, decoded to
+//                          the caller's buffer or to a staging slot
+//                          (snappy_ranges.hip holds the check, clip and status kernels)
 //
 // The hash table holds block-relative positions; 0 is a valid candidate,
 // exactly as in the reference (snappy_compression.c:259-265).
@@ -2527,14 +2531,29 @@ struct K4Record {
 // record of a batch, so the units of this stream -- status[units] and
 // status[units + 1] are pass 2's ticket counter and pass 1's defer flag -- are
 // the record's own blocks (`units`), not the grid of the launch.
-template <bool BACK, bool REC = false, bool LONG = false>
+//
+// RANGE (one unit of a range decode, snappy_ranges.hip; pass 1 only): the unit is
+// named by the stream's own index and number, but only a window of the stream is
+// resident and the launch's grid is the plan, not the stream.  So the bound of
+// every read is the window's end (rng.c_end, from the 4-aligned comp) instead of
+// the index's last entry, and the unit's failure goes to its range's key
+// (atomicMin of (unit + 1) << 8 | -status: the lowest failing unit wins) instead
+// of status[u] and the defer flag.  A deferred unit is final here:
+// ERR_DEPENDENT in the SINGLE layout, ERR_OFFSET in STREAMS.
+struct K4Range {
+    uint64_t c_end;
+    unsigned long long *key;
+};
+
+template <bool BACK, bool REC = false, bool LONG = false, bool RANGE = false>
 __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const uint64_t *__restrict__ offsets,
                                         uint64_t n, uint32_t unit, uint32_t hdr_mode, uint64_t header_value,
                                         uint32_t allow_back, uint32_t bias, uint8_t *__restrict__ out,
                                         int32_t *__restrict__ status, uint32_t u, const K4Record rec = {},
-                                        const uint32_t units = 0)
+                                        const uint32_t units = 0, const K4Range rng = {})
 {
     static_assert(!(BACK && REC), "records are their own streams: there is no second pass");
+    static_assert(!(RANGE && (BACK || REC || LONG)), "a range unit is a pass 1 unit of the stream's own index");
     // copy source positions: relative to the unit start, negative = an earlier unit (pass 2 only)
     using SrcT = typename std::conditional<BACK, int64_t, uint32_t>::type;
     __shared__ __attribute__((aligned(16))) uint32_t lds[kK4Lds / 4];
@@ -2554,7 +2573,7 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
     // straddling out) as far as the stream goes
     // (the last entry is the stream end: no read goes past it, whatever the
     // entries in between say -- a corrupt index fails as TRUNCATED, not a fault)
-    const uint64_t c_end = REC ? c1n : (offsets[(n + unit - 1) / unit] & kIdxOffMask) + bias;
+    const uint64_t c_end = RANGE ? rng.c_end : REC ? c1n : (offsets[(n + unit - 1) / unit] & kIdxOffMask) + bias;
     uint64_t c1 = skip1 ? c_end : c1n;
     if (c1 > c_end) c1 = c_end;
     if (c1 > c0 + 0x7FFFFFFFull) c1 = c0 + 0x7FFFFFFFull;
@@ -3220,6 +3239,10 @@ __device__ __forceinline__ void k4_body(const uint8_t *__restrict__ comp, const 
             status[u] = st;
             if (st != SNAPPY_ST_OK) atomicMin(rec.first, ((unsigned long long)u << 8) | (uint32_t)-st);
         }
+    } else if constexpr (RANGE) {
+        if (st == SNAPPY_ST_DEFER) st = allow_back ? SNAPPY_ST_DEPENDENT : SNAPPY_ST_OFFSET;
+        if (lane == 0 && st != SNAPPY_ST_OK)
+            atomicMin(rng.key, (((unsigned long long)u + 1) << 8) | (uint32_t)-st);
     } else {
         if (lane == 0) status[u] = st;
         // status[units + 1] = pass 2 has work (status[units] is pass 2's ticket counter)
@@ -3376,6 +3399,34 @@ __global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_back_lunits(const K4L
     if (blk >= k.nblk || k.status[blk] != SNAPPY_ST_DEFER) return;
     k4_body<true, false, true>(k.comp, k.table, k.n, SNAPPY_BLOCK, SNAPPY_HDR_FIRST_UNIT, k.n, 1u, k.bias, k.out,
                                k.status, blk, {}, k.nblk);
+}
+
+// Range decode: workgroup b decodes planned unit first + b -- stream unit e.unit
+// for range e.range -- through k4_body with the stream's own index.  comp_at is
+// the address the stream's byte 0 would have (d_comp - comp_origin, an integer:
+// it may lie outside any allocation), so the index's stream-relative offsets
+// address the window as they are; the check pass (kr0_range_check) has refused
+// every range with a unit whose bytes are not all inside the window, and such a
+// range (key < 256) decodes nothing.  An interior unit's byte 0 lands at out +
+// e.land; an edge unit decodes its whole block into its staging slot.
+__global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_decode_range_units(const K4RangeArgs a)
+{
+    const snappy_range_unit *const e = a.plan + a.first + blockIdx.x;
+    const uint32_t r = rfl(e->range), edge = rfl(e->edge);
+    const uint64_t u = rfl64(e->unit), land = rfl64(e->land);
+    unsigned long long *const key = a.keys + r;
+    if (rfl64(*reinterpret_cast<const volatile unsigned long long *>(key)) < 256) return;
+    const uint32_t bias = (uint32_t)(a.comp_at & 3);
+    const uint8_t *const comp = reinterpret_cast<const uint8_t *>(a.comp_at - bias);
+    const uintptr_t dst = edge ? reinterpret_cast<uintptr_t>(a.slots) + (uint64_t)((edge - 1) % a.slot_cap) * SNAPPY_BLOCK
+                               : reinterpret_cast<uintptr_t>(a.out) + land;
+    K4Range rng;
+    rng.c_end = a.win_end + bias;
+    rng.key = key;
+    // (k4_body writes at out + u * unit)
+    k4_body<false, false, false, true>(comp, a.offsets, a.n, a.unit, a.hdr_mode, a.n, a.allow_back, bias,
+                                       reinterpret_cast<uint8_t *>(dst - u * a.unit), nullptr, (uint32_t)u, {}, 0,
+                                       rng);
 }
 #endif
 // ---------------------------------------------------------------------------

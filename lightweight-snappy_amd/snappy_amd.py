@@ -36,6 +36,7 @@ ERR_UNSUPPORTED = -9
 ERR_TIMEOUT = -10
 ERR_INDEX = -11
 ERR_CHECKSUM = -12
+ERR_DEPENDENT = -13  # range decode: a block of the range needs bytes of an earlier block
 FRAME_NO_IDENTIFIER = 1  # compress_frame_*: this buffer continues a framed stream
 FRAME_IDENTIFIER = bytes.fromhex("ff060000734e61507059")
 CONTAINER_HADOOP = 0  # Hadoop SnappyCodec blocks (.snappy files)
@@ -67,6 +68,7 @@ _NAMES = {
     ERR_TIMEOUT: "block dependency wait timed out",
     ERR_INDEX: "sidecar index does not fit the stream",
     ERR_CHECKSUM: "chunk CRC-32C mismatch",
+    ERR_DEPENDENT: "a block of the range needs an earlier block",
 }
 
 # every function include/*.h declares, with its ctypes signature
@@ -174,6 +176,13 @@ _SIGS = {
     "snappy_amd_decompress_long_records_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                                              _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                                              _c.c_void_p, _c.c_void_p, _c.c_int]),
+    # range decode
+    "snappy_amd_decompress_ranges_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_size_t, _c.c_void_p,
+                                                       _c.c_size_t, _c.c_uint32, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                                       _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int]),
+    "snappy_decompress_range_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_uint64,
+                                                  _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "snappy_decompress_file_range": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p]),
     "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
     "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     # Hadoop / snappy-java containers
@@ -501,6 +510,26 @@ def decompress_indexed(data, index_file: bytes) -> bytes:
     return out.raw[: got.value]
 
 
+def decompress_range(data, start: int, length: int, index_file: Optional[bytes] = None) -> bytes:
+    """Bytes [start, start + length) of decompress(data).  With index_file (the
+    sidecar file's bytes) only the compressed bytes of the blocks the range touches
+    are uploaded; without it the stream is uploaded whole and indexed on the GPU."""
+    p, n, keep = _buf(data)
+    if index_file is not None:
+        ip, ilen, ikeep = _buf(index_file)
+        if ilen == 0:
+            raise SnappyError(ERR_INDEX, "decompress_range")
+    else:
+        ip, ilen = None, 0
+    if start < 0 or length < 0:
+        raise SnappyError(ERR_ARG, "decompress_range")
+    out = ctypes.create_string_buffer(max(length, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_decompress_range_buffer(p, n, ip, ilen, start, length, out, length, ctypes.byref(got)),
+           "decompress_range")
+    return out.raw[: got.value]
+
+
 # ---- the reference's FILE*-level calls over Python binary files -------------
 def snappy_compress(file_input: BinaryIO, input_size: int, file_compressed: BinaryIO) -> None:
     """snappy_compress (src/snappy_compression.c:414): reads file_input from its
@@ -643,6 +672,35 @@ class Codec:
         self._bind_stream()
         self.decompress_ptr(comp.data_ptr(), offsets.data_ptr(), n, chunk, layout, out.data_ptr())
         return out[:n]
+
+    def decompress_ranges_tensor(self, comp, offsets, n: int, ranges, out=None, chunk: int = BLOCK,
+                                 layout: int = SINGLE, comp_origin: int = 0, want_status: bool = True):
+        """Decode the byte ranges `ranges` -- a list or array of (start, length,
+        out_offset) -- of the stream whose full index is `offsets` (int64 CUDA
+        tensor) and whose compressed bytes [comp_origin, comp_origin + comp.numel())
+        are `comp`.  Range i lands at out[out_offset_i : out_offset_i + length_i];
+        out=None allocates max(out_offset + length) bytes.  Returns (out, status): an int32 CUDA tensor of each range's status
+        (self.last_ranges_status = the first failure), or (out, None) with
+        want_status=False, which queues the work and reads nothing back."""
+        import numpy as np
+        assert comp.is_cuda and comp.dtype == torch.uint8 and comp.is_contiguous()
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous()
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 3))
+        count = r.shape[0]
+        if out is None:
+            need = int((r[:, 1] + r[:, 2]).max()) if count else 0
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=comp.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=comp.device) if want_status else None
+        self._bind_stream()
+        rc = lib().snappy_amd_decompress_ranges_device(
+            self._h, ctypes.c_void_p(comp.data_ptr()), comp_origin, comp.numel(), ctypes.c_void_p(offsets.data_ptr()),
+            n, chunk, layout, r.ctypes.data_as(ctypes.c_void_p), count, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(status.data_ptr()) if want_status else None, 1 if want_status else 0)
+        self.last_ranges_status = rc
+        if rc in (ERR_DEVICE, ERR_ARG) and not (want_status and count and rc == ERR_ARG):
+            raise SnappyError(rc, "decompress_ranges_device")
+        return out, (status[:count] if want_status else None)
 
     def index_tensor(self, comp):
         """Block index of a SINGLE-layout stream (e.g. a reference .snp)."""

@@ -32,8 +32,18 @@ the container compress; decompress_long_records_device with NULL block tables on
 the container's own chunk tables for the container decode with tables given.
 container_index_device alone is reported per chunk.
 
+and range decode, leg r, on the SINGLE stream of the N bytes:
+
+  r_range_whole   one range [1, N - 1)                       \  vs  the SINGLE decode of the
+  r_range_1mib    one 1 MiB range at an unaligned start      /  same stream in the same round
+  r_range_16k_4k  16,384 ranges of 4,096 bytes at seeded random starts: the time and the
+                  bytes decoded per byte delivered (no yardstick)
+
+Every range's out_offset agrees with its start mod 16 (16-byte stores, as the whole
+decode writes).
+
 Prints one JSON line and writes it to profiles/<tag>.json when a tag is given:
-    python tools/records_bench.py [n_bytes] [reps] [tag] [legs, default abcdefg; hx on request]
+    python tools/records_bench.py [n_bytes] [reps] [tag] [legs, default abcdefg; hx and r on request]
 Run under rocprofv3 --kernel-trace --stats (a run of its own) for per-kernel times."""
 import json
 import os
@@ -84,7 +94,7 @@ legs = {"a": uniform(32768), "b": uniform(65536), "c": log_uniform(), "d": unifo
         "h": uniform(snappy_amd.CONTAINER_BLOCK[snappy_amd.CONTAINER_HADOOP]),
         "x": uniform(snappy_amd.CONTAINER_BLOCK[snappy_amd.CONTAINER_XERIAL])}
 legs = {k: v[v[:, 1] > 0] for k, v in legs.items() if k in which}
-max_count = max(len(v) for v in legs.values())
+max_count = max([len(v) for v in legs.values()] + [1])
 out = torch.empty(max(snappy_amd.max_records_output(n, max_count), snappy_amd.max_long_records_output(n, max_count),
                       codec.max_output(n, snappy_amd.BLOCK, snappy_amd.SINGLE)), dtype=torch.uint8, device="cuda")
 back = torch.empty(n, dtype=torch.uint8, device="cuda")
@@ -239,6 +249,38 @@ def long_round(k, r):
     return t
 
 
+def range_sets():
+    rng = np.random.default_rng(2468)
+    starts = rng.integers(0, n - 4096, 16384)
+    many = np.stack([starts, np.full(16384, 4096), np.arange(16384) * 4112 + starts % 16], axis=1).astype(np.uint64)
+    one = min(300 * (1 << 20) + 12345, n // 3 + 1)
+    ln = min(1 << 20, n - one)
+    touched = int(((starts + 4095) // snappy_amd.BLOCK - starts // snappy_amd.BLOCK + 1).sum())
+    return {"range_whole": np.array([[1, n - 2, 1]], dtype=np.uint64),
+            "range_1mib": np.array([[one, ln, one % 16]], dtype=np.uint64), "range_16k_4k": many}, touched
+
+
+def decode_ranges(ranges):
+    codec.decompress_ranges_tensor(out[: state["slen"]], state["single_offs"], n, ranges, out=back)
+    assert codec.last_ranges_status == 0
+
+
+def range_round(r):
+    """one round of the range legs and of their yardstick, the SINGLE decode -> {name: ms}"""
+    if "ranges" not in state:
+        state["ranges"], state["touched"] = range_sets()
+        compress_single()
+    t = {"decode_single": timed(decode_single)}
+    for name, ranges in state["ranges"].items():
+        if r == 1:
+            back.zero_()
+        t[name] = timed(decode_ranges, ranges)
+        if r == 1:
+            for a, ln, oo in ranges[:: max(1, len(ranges) // 64)].tolist():
+                assert torch.equal(back[oo:oo + ln], x[a:a + ln]), f"leg r: {name} differs"
+    return t
+
+
 def compress_streams(chunk):
     state["plen"] = codec.compress_ptr(x.data_ptr(), n, chunk, snappy_amd.STREAMS, out.data_ptr(), state["soffs"].data_ptr())
 
@@ -263,6 +305,11 @@ def median(v):
 ms = {}
 with torch.cuda.stream(stream):
     for r in range(reps + 2):  # two warm-up rounds (code objects, scratch growth)
+        if "r" in which:
+            t = range_round(r)
+            if r >= 2:
+                for name, v in t.items():
+                    ms.setdefault(f"r_{name}", []).append(v)
         for k in legs:
             if k in LONG or k in CONTAINER:
                 t = long_round(k, r) if k in LONG else container_round(k, r)
@@ -321,6 +368,11 @@ for k in legs:
         res[f"{k}_decode_table_ratio"] = med[f"{k}_decode_container_table"] / med[f"{k}_decode_long_null"]
         res[f"{k}_decode_table_extra_ms"] = med[f"{k}_decode_container_table"] - med[f"{k}_decode_long_null"]
         res[f"{k}_index_us_per_chunk"] = 1e3 * med[f"{k}_index_container"] / dev[k]["count"]
+if "r" in which:
+    for name in ("range_whole", "range_1mib"):
+        res[f"r_{name}_minus_single_ms"] = med[f"r_{name}"] - med["r_decode_single"]
+    res["r_range_whole_ratio"] = med["r_range_whole"] / med["r_decode_single"]
+    res["r_16k_4k_decoded_per_delivered"] = state["touched"] * snappy_amd.BLOCK / (16384 * 4096)
 line = json.dumps(res)
 print(line)
 if tag:
