@@ -547,6 +547,92 @@ int snappy_frame_uncompressed_length(const uint8_t *in, size_t n, uint64_t *len)
 int snappy_compress_file_framed(FILE *file_input, unsigned long long input_size, FILE *file_compressed);
 int snappy_decompress_file_framed(FILE *file_input, FILE *file_decompressed);
 
+/* ---- range decode of a framed stream: seek table, CRC-checked slices ------ */
+/* Random access into a framed stream.  Every data chunk is its own raw stream
+ * of at most 65,536 bytes under its own CRC, so any chunk decodes alone
+ * (ERR_DEPENDENT cannot happen) and a slice comes back verified.  Chunks may
+ * have any decoded length, so a byte position is found by a search in the
+ * stream's seek table: d_starts, nchunks + 1 u64 entries beside the chunk table,
+ * entry i = the decoded position of data chunk i's first byte, entry nchunks =
+ * the decoded length.
+ *
+ * frame_seek_device builds it from a chunk table: every entry's header is
+ * checked as decompress_frame_device checks it (the same codes, the first
+ * failing entry's), then the lengths are scanned.  *n_out = the decoded length.
+ * compress_frame_device's own streams give starts[i] = min(65536 i, n).
+ * snappy_frame_tables is the same on host memory, with no kernel: the chunk
+ * walk of frame_index_device and both tables (room for max_chunks entries each,
+ * the closing ones included; either may be NULL). */
+int snappy_amd_frame_seek_device(snappy_amd_ctx *ctx, const void *d_frame, size_t clen, const uint64_t *d_chunks,
+                                 size_t nchunks, uint64_t *d_starts, size_t *n_out);
+int snappy_frame_tables(const uint8_t *in, size_t n, uint64_t *chunks, uint64_t *starts, size_t max_chunks,
+                        size_t *nchunks_out, uint64_t *len);
+/* d_window[0, comp_bytes) holds the stream's bytes [comp_origin, comp_origin +
+ * comp_bytes): the resident window.  d_chunks and d_starts (device) may be any
+ * contiguous sub-table, nchunks + 1 entries each, of the stream's tables:
+ * positions and starts stay absolute.  Range i (host memory) writes the stream's
+ * decoded bytes [start, start + length) to d_out[out_offset, out_offset + length);
+ * length == 0 is OK and touches nothing.  The call is synchronous: the tables are
+ * in HBM, so the plan (csrc/snappy_frame_ranges.h) runs there and 64 bytes are
+ * read back to size the launches (a second read, of 8 bytes per launch group,
+ * only with more edge units than staging slots).
+ *
+ * A range's span: its first chunk u0 is the last i with starts[i] <= start, its
+ * last chunk u1 the last i with starts[i] <= start + length - 1, both by binary
+ * search.  Every chunk u0..u1 is one decode unit; an empty chunk inside the span
+ * is skipped (not read, no effect on the status).  A chunk that lies wholly
+ * inside its range decodes straight into d_out; an edge chunk decodes whole into
+ * a staging slot, is CRC-checked there, and its wanted part is copied out (the
+ * staging rule of decompress_ranges_device: at most 1,024 slots, more edge units
+ * in successive launches).  Scratch: 64 MiB at most, 76 bytes per unit, 72 per range.
+ *
+ * d_status (count i32, device; may be NULL) gets every range's status; the call
+ * returns the first failing range's.  In this order:
+ *   ERR_ARG        the range leaves [starts[0], starts[nchunks])
+ *   ERR_CAPACITY   the output range leaves [0, out_bytes)
+ *  (A seek table that is not sorted is not refused here: the search still gives
+ *  u0 <= u1.  Its units are refused in the header stage, below.)
+ *  then the header stage, over every non-empty unit before anything is decoded; a
+ *  range with a failing unit decodes and stores nothing, and its status is its
+ *  lowest failing unit's:
+ *   ERR_TRUNCATED  the chunk's bytes [chunks[u], chunks[u] + 4 + len) are not all
+ *                  inside the window
+ *   ERR_HEADER, ERR_UNSUPPORTED, ERR_OVERRUN  the chunk's own header, as the
+ *                  framed decoder reports it
+ *   ERR_INDEX      the entry is not a data chunk; its decoded length is not
+ *                  starts[u + 1] - starts[u]; it runs past chunks[u + 1]; or the
+ *                  seek table contradicts itself about the unit, as one that is
+ *                  not sorted does (a chunk of more than 65,536 bytes, one inside
+ *                  the span that begins before the range or ends after it, an
+ *                  empty first or last chunk)
+ *  then the decode: element errors and ERR_CHECKSUM, the lowest failing chunk of
+ *  the range; a CRC counts only where the chunk's decode succeeded.
+ * Guarantees: no byte of d_out outside the accepted ranges' output is written,
+ * whatever the tables say (a range that fails while it decodes may leave part of
+ * its own output written); no read leaves the window, except within the aligned
+ * dword that holds its first byte.  A range's status is what
+ * decompress_frame_device returns for a stream made of the identifier and exactly
+ * that range's non-empty chunks.  What success proves: each touched chunk agrees
+ * with its own header and CRC.  It does not prove that the tables are the
+ * stream's tables -- a table of another stream with the same chunk positions and
+ * lengths passes -- that stays the caller's word, as in decompress_ranges_device. */
+int snappy_amd_decompress_frame_ranges_device(snappy_amd_ctx *ctx, const void *d_window, uint64_t comp_origin,
+                                              size_t comp_bytes, const uint64_t *d_chunks, const uint64_t *d_starts,
+                                              size_t nchunks, const snappy_amd_range *ranges, size_t count,
+                                              void *d_out, size_t out_bytes, int32_t *d_status);
+/* Host forms: exactly bytes [start, start + length) of
+ * snappy_decompress_frame_buffer's output, or SNAPPY_AMD_ERR_ARG for a range that
+ * leaves it.  The buffer form walks the headers on the host and uploads only the
+ * chunks of the span and their sub-tables.  The FILE* form hops from header to
+ * header with 16-byte reads from the current position (no payload is read, and
+ * the walk stops at the chunk holding the range's last byte: a damaged chunk
+ * after it is never seen, one before it is the walk's error), then reads the
+ * span's chunks with one seek and one read; a file_input that cannot seek is
+ * SNAPPY_AMD_ERR_UNSUPPORTED. */
+int snappy_decompress_frame_range_buffer(const uint8_t *in, size_t n, uint64_t start, size_t length, uint8_t *out,
+                                         size_t cap, size_t *out_len);
+int snappy_decompress_file_frame_range(FILE *file_input, uint64_t start, uint64_t length, FILE *file_out);
+
 /* ---- Hadoop and snappy-java container streams ---------------------------- */
 /* The two length-prefixed containers most Snappy files on disk are in: the
  * .snappy files of Hadoop's SnappyCodec (Hive, Spark) and the streams of

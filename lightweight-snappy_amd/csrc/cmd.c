@@ -15,8 +15,10 @@
  * -R start:length (an addition): with -d write only the decoded bytes [start,
  * start + length) of the stream.  With -i only the compressed bytes of the
  * blocks the range touches are read from infile (which must be seekable);
- * without -i the stream is read whole and indexed on the GPU.  Not with -c, -b,
- * -f or -F.
+ * without -i the stream is read whole and indexed on the GPU.  With -f the
+ * stream is a framed one: its chunk headers are read up to the range's last
+ * chunk, then only the range's chunks (infile must be seekable).  Not with -c,
+ * -b or -F.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -38,7 +40,8 @@ static void usage(void)
             "-i -c: also write outfile.idx (block index); -d: use infile.idx\n"
             "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n"
             "-F hadoop|xerial with -c or -d: the Hadoop SnappyCodec / snappy-java container\n"
-            "-R start:length with -d: only the decoded bytes [start, start + length) (-i: read only their blocks)\n");
+            "-R start:length with -d: only the decoded bytes [start, start + length) (-i: read only their blocks;\n"
+            "   -f: of a framed stream, reading only their chunks)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -91,7 +94,7 @@ int main(int argc, char *argv[])
     if (indexed && mode == M_BST) usage();  /* -b writes no block index */
     if (framed && (indexed || mode == M_BST)) usage();  /* a framed stream has its chunk headers; -b is unframed */
     if (container >= 0 && (framed || indexed || mode == M_BST)) usage();  /* one file format at a time */
-    if (ranged && (mode != M_DECOMPRESS || compress_flag || framed || container >= 0)) usage();  /* -R: a raw stream's decode */
+    if (ranged && (mode != M_DECOMPRESS || compress_flag || container >= 0)) usage();  /* -R: a raw or framed stream's decode */
     const char *in_name = argv[argc - 2], *out_name = argv[argc - 1];
     FILE *in = open_or_die(in_name, "rb");
     FILE *out = open_or_die(out_name, "wb");
@@ -109,6 +112,9 @@ int main(int argc, char *argv[])
     if (container >= 0) {
         rc = mode == M_COMPRESS ? snappy_compress_file_container(in, in_size, 0, container, out)
                                 : snappy_decompress_file_container(in, container, out);
+    } else if (framed && ranged) {
+        rc = snappy_decompress_file_frame_range(in, r_start, r_length, out);
+        if (rc != 0) fprintf(stderr, "snappy_decompress_file_frame_range: error %d\n", rc);
     } else if (framed) {
         rc = mode == M_COMPRESS ? snappy_compress_file_framed(in, in_size, out) : snappy_decompress_file_framed(in, out);
     } else if (mode == M_COMPRESS && idx) {

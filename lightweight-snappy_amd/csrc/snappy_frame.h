@@ -18,6 +18,27 @@
 #define SNAPPY_FRAME_CHUNK_MAX 65536u  // uncompressed bytes of one data chunk
 #define SNAPPY_FRAME_WINDOW 16u        // bytes of a chunk one step looks at
 
+#if defined(__HIPCC__)
+// dst[0, n) = src[0, n), one wave; 16-byte stores on the aligned middle (the payload
+// copies of the unframe pass and of the range decode's stored chunks)
+__device__ __forceinline__ void snappy_frame_wave_copy(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t lane)
+{
+    uint32_t head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
+    if (head > n) head = n;
+    if (lane < head) dst[lane] = src[lane];
+    dst += head;
+    src += head;
+    n -= head;
+    const uint32_t nv = n >> 4;
+    for (uint32_t i = lane; i < nv; i += 64) {
+        uint4 v;
+        __builtin_memcpy(&v, src + 16 * (size_t)i, 16);
+        *reinterpret_cast<uint4 *>(dst + 16 * (size_t)i) = v;
+    }
+    for (uint32_t i = 16 * nv + lane; i < n; i += 64) dst[i] = src[i];
+}
+#endif
+
 // varint(v) and literal-tag lengths for v <= 65536 (an uncompressed chunk
 // rewritten as a raw stream: varint(len) ++ one literal element)
 SNAPPY_FRAME_FN uint32_t snappy_frame_varint_len(uint32_t v) { return v < 128u ? 1u : v < 16384u ? 2u : 3u; }

@@ -9,6 +9,7 @@
 //   KF4  kf4_scan        per data chunk: header checks, decoded length, scratch bytes
 //        kf4_gather      payloads -> contiguous scratch, as SNAPPY_AMD_STREAMS units
 //        kf4_verify      stored CRC against KF1's over the decoded bytes
+//   KF5  kf5_seek_lens   kf4_scan's lengths for the seek table (their K3 scan is the table)
 //
 // The match finder, the scan, the emitter (K1r64, K3, K2) and the decoder (K4)
 // are the unframed path's kernels, unchanged (the compress ones through the
@@ -307,24 +308,6 @@ __global__ __launch_bounds__(256) void kf4_scan(const uint8_t *__restrict__ f, u
     info[i] = o;
 }
 
-// dst[0, n) = src[0, n), one wave; 16-byte stores on the aligned middle
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t lane)
-{
-    uint32_t head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
-    if (head > n) head = n;
-    if (lane < head) dst[lane] = src[lane];
-    dst += head;
-    src += head;
-    n -= head;
-    const uint32_t nv = n >> 4;
-    for (uint32_t i = lane; i < nv; i += 64) {
-        uint4 v;
-        __builtin_memcpy(&v, src + 16 * (size_t)i, 16);
-        *reinterpret_cast<uint4 *>(dst + 16 * (size_t)i) = v;
-    }
-    for (uint32_t i = 16 * nv + lane; i < n; i += 64) dst[i] = src[i];
-}
-
 constexpr uint32_t kF4Waves = 4;
 
 // One wave per unit (a data chunk that decodes to >= 1 byte, checked by
@@ -364,7 +347,7 @@ __global__ __launch_bounds__(64 * kF4Waves) void kf4_gather(const uint8_t *__res
             for (uint32_t b = 0; b < k; b++) dst[b] = hb[b];
         dst += k;
     }
-    wave_copy(dst, h + 8, plen, lane);
+    snappy_frame_wave_copy(dst, h + 8, plen, lane);
 }
 
 __global__ __launch_bounds__(256) void kf4_verify(const uint8_t *__restrict__ f, const uint64_t *__restrict__ chunks,
@@ -376,6 +359,19 @@ __global__ __launch_bounds__(256) void kf4_verify(const uint8_t *__restrict__ f,
     const uint8_t *h = f + chunks[i] + 4;
     const uint32_t stored = (uint32_t)h[0] | ((uint32_t)h[1] << 8) | ((uint32_t)h[2] << 16) | ((uint32_t)h[3] << 24);
     cst[i] = stored == crc[i] ? SNAPPY_AMD_OK : SNAPPY_AMD_ERR_CHECKSUM;
+}
+
+// KF5: the seek table's input.  One thread per entry kf4_scan looked at: its decoded
+// length for the scan (0 where it failed), and the first failing entry as
+// entry << 8 | -status (atomicMin; ~0 before).
+__global__ __launch_bounds__(256) void kf5_seek_lens(const FrameInfo *__restrict__ info, uint64_t nchunks,
+                                                     uint32_t *__restrict__ lens, unsigned long long *__restrict__ first)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nchunks) return;
+    const FrameInfo o = info[i];
+    lens[i] = o.st == SNAPPY_AMD_OK ? o.dlen : 0u;
+    if (o.st != SNAPPY_AMD_OK) atomicMin(first, ((unsigned long long)i << 8) | (uint32_t)-o.st);
 }
 
 uint32_t blocks_of(uint64_t items, uint32_t per) { return (uint32_t)((items + per - 1) / per); }
@@ -396,6 +392,14 @@ void launch_kf1(snappy_amd_ctx *c, const void *d_base, const uint64_t *d_off_len
 }
 
 }  // namespace
+
+// KF1 for the range decode of framed streams (snappy_frame_ranges.hip; declared in snappy_kernels.h)
+void snappy_amd::frame_launch_crc32c(hipStream_t stream, const void *d_base, const uint64_t *d_off_len, uint64_t count,
+                                     int masked, uint32_t *d_crc)
+{
+    hipLaunchKernelGGL(kf1_crc32c, dim3(blocks_of(count, kF1Waves)), dim3(64 * kF1Waves), 0, stream,
+                       static_cast<const uint8_t *>(d_base), d_off_len, count, 0ull, 0ull, masked ? 1u : 0u, d_crc);
+}
 
 extern "C" {
 
@@ -471,6 +475,42 @@ int snappy_amd_frame_index_device(snappy_amd_ctx *c, const void *d_frame, size_t
     if (n_out) *n_out = (size_t)res[1];
     if (nchunks_out) *nchunks_out = (size_t)res[2];
     return (int)res[0];
+}
+
+int snappy_amd_frame_seek_device(snappy_amd_ctx *c, const void *d_frame, size_t clen, const uint64_t *d_chunks,
+                                 size_t nchunks, uint64_t *d_starts, size_t *n_out)
+{
+    if (!c || (!d_frame && clen) || (!d_chunks && nchunks) || !d_starts || nchunks > 0x7FFFFFFFull)
+        return SNAPPY_AMD_ERR_ARG;
+    if (n_out) *n_out = 0;
+    int rc = frame_call_begin(c);
+    if (rc) return rc;
+    // head (the first failure, the total) | info | lens
+    const size_t nc = nchunks;
+    if ((rc = grow(reinterpret_cast<void **>(&c->f_meta), &c->f_meta_cap, 64 + nc * (sizeof(FrameInfo) + 4)))) return rc;
+    unsigned long long *d_head = reinterpret_cast<unsigned long long *>(c->f_meta);
+    FrameInfo *d_info = reinterpret_cast<FrameInfo *>(c->f_meta + 64);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(d_info + nc);
+    HIP_OK(hipMemsetAsync(d_head, 0xFF, sizeof(uint64_t), c->stream));
+    if (nc) {
+        hipLaunchKernelGGL(kf4_scan, dim3(blocks_of(nc, 256)), dim3(256), 0, c->stream,
+                           static_cast<const uint8_t *>(d_frame), (uint64_t)clen, d_chunks, (uint64_t)nc, d_info);
+        hipLaunchKernelGGL(kf5_seek_lens, dim3(blocks_of(nc, 256)), dim3(256), 0, c->stream, d_info, (uint64_t)nc,
+                           d_lens, d_head);
+    }
+    // the exclusive scan of the lengths is the table; its total the decoded length
+    if (nc <= SNAPPY_K3_WAVE_MAX)
+        hipLaunchKernelGGL(k3_scan_wave, dim3(1), dim3(64), 0, c->stream, d_lens, (uint64_t)nc, d_starts,
+                           reinterpret_cast<uint64_t *>(d_head + 1));
+    else
+        hipLaunchKernelGGL(k3_scan, dim3(1), dim3(1024), 0, c->stream, d_lens, (uint64_t)nc, d_starts,
+                           reinterpret_cast<uint64_t *>(d_head + 1));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(c->h_total, d_head, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (c->h_total[0] != ~0ull) return -(int)(c->h_total[0] & 0xFF);
+    if (n_out) *n_out = (size_t)c->h_total[1];
+    return SNAPPY_AMD_OK;
 }
 
 int snappy_amd_decompress_frame_device(snappy_amd_ctx *c, const void *d_frame, size_t clen, const uint64_t *d_chunks,

@@ -174,6 +174,43 @@ struct K4RangeArgs {
 // K4 pass 1 over planned units [first, first + grid x), one wave each
 __global__ void kr4_decode_range_units(const K4RangeArgs a);
 
+// What the range decode of a framed stream shares with the calls it is built from
+// (host functions, hidden: not part of the C ABI).  snappy_ranges.hip: the staging
+// slots of a call (SNAPPY_RANGES_SLOT_CAP, or SNAPPY_AMD_RANGE_SLOTS), KG6 kr6_clip
+// over planned units [first, first + units) and KG7 kr7_range_status over `count`
+// keys.  snappy_frame.hip: KF1 over `count` (offset, length) entries from `base`.
+__attribute__((visibility("hidden"))) uint32_t ranges_slot_cap();
+__attribute__((visibility("hidden"))) void ranges_launch_clip(hipStream_t stream, const snappy_range_unit *plan,
+                                                              uint64_t first, uint32_t units,
+                                                              const unsigned long long *keys, const uint8_t *slots,
+                                                              uint32_t slot_cap, uint8_t *out);
+__attribute__((visibility("hidden"))) void ranges_launch_status(hipStream_t stream, const unsigned long long *keys,
+                                                                uint64_t count, int32_t *status,
+                                                                unsigned long long *first);
+__attribute__((visibility("hidden"))) void frame_launch_crc32c(hipStream_t stream, const void *d_base,
+                                                               const uint64_t *d_off_len, uint64_t count, int masked,
+                                                               uint32_t *d_crc);
+
+// ---- range decode of a framed stream (snappy_frame_ranges.hip): the planned units
+// of snappy_frame_ranges.h, each one data chunk of the stream
+struct K4FrameArgs {
+    uintptr_t comp_at;              // the address of the stream's byte 0: d_window - comp_origin (any alignment)
+    const uint64_t *chunks;         // the chunk table and the seek table (or sub-tables: positions are absolute)
+    const uint64_t *starts;
+    uint32_t slot_cap;              // staging slots in use (edge k uses slot (k - 1) % slot_cap)
+    const snappy_range_unit *plan;  // the planned units
+    uint64_t first;                 // this launch's first planned unit
+    unsigned long long *keys;       // per range: ~0, < 256 refused before any decode (-status), else the
+                                    // lowest failing chunk: (chunk + 1) << 8 | -status
+    int32_t *ustatus;               // per planned unit: its decode status (the CRC counts only where it is OK);
+                                    // the header stage left 1 there for a unit that is not decoded and 2
+                                    // for a stored chunk (the copy kernel's, which then writes 0)
+    uint8_t *slots;
+    uint8_t *out;
+};
+// K4 pass 1 over planned units [first, first + grid x), one wave per compressed chunk
+__global__ void kr4_decode_frame_units(const K4FrameArgs a);
+
 #ifndef SNAPPY_K5_CHUNK
 #define SNAPPY_K5_CHUNK 16384
 #endif

@@ -23,6 +23,9 @@
 //                          a unit is one block of the stream for one range, decoded to
 //                          the caller's buffer or to a staging slot
 //                          (snappy_ranges.hip holds the check, clip and status kernels)
+//   KH  kr4_decode_frame_units: the record body of K4 pass 1 over the planned units of a
+//                          range decode of a framed stream -- a unit is one data chunk
+//                          (snappy_frame_ranges.hip holds the plan, header, CRC and copy kernels)
 //
 // The hash table holds block-relative positions; 0 is a valid candidate,
 // exactly as in the reference (snappy_compression.c:259-265).
@@ -3427,6 +3430,42 @@ __global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_decode_range_units(co
     k4_body<false, false, false, true>(comp, a.offsets, a.n, a.unit, a.hdr_mode, a.n, a.allow_back, bias,
                                        reinterpret_cast<uint8_t *>(dst - u * a.unit), nullptr, (uint32_t)u, {}, 0,
                                        rng);
+}
+
+// Range decode of a framed stream: workgroup b decodes planned unit p = first + b
+// -- data chunk e.unit for range e.range -- as a record of its own (k4_body<false,
+// true>, the instantiation of kr4_decode_records): the payload behind the chunk's
+// 8 header bytes, at any alignment, to out + e.land (an interior unit) or to its
+// staging slot (an edge unit).  The header stage (snappy_frame_ranges.hip) has
+// checked the chunk against the window and both tables and left ustatus[p] != 0
+// for every unit that is not to be decoded here (1: an empty chunk, a refused
+// range; 2: a stored chunk, type 01, left to the copy kernel), so such a wave
+// leaves without touching the window.  The record's number is chunk
+// + 1, so its failure goes to the range's key as (chunk + 1) << 8 | -status and the
+// lowest failing chunk wins; its status word is ustatus[p].
+__global__ __launch_bounds__(64, SNAPPY_K4_WAVES) void kr4_decode_frame_units(const K4FrameArgs a)
+{
+    const uint64_t p = a.first + blockIdx.x;
+    if (rfl((uint32_t)a.ustatus[p]) != 0) return;
+    const snappy_range_unit *const e = a.plan + p;
+    const uint32_t r = rfl(e->range), edge = rfl(e->edge);
+    const uint64_t u = rfl64(e->unit), land = rfl64(e->land);
+    const uint64_t pos = rfl64(a.chunks[u]);
+    const uint8_t *const h = reinterpret_cast<const uint8_t *>(a.comp_at + pos);
+    const uint32_t len =rfl((uint32_t)h[1] | ((uint32_t)h[2] << 8) | ((uint32_t)h[3] << 16));
+    const uint32_t bias = (uint32_t)(a.comp_at & 3);
+    const uint8_t *const comp = reinterpret_cast<const uint8_t *>(a.comp_at - bias);
+    K4Record rec;
+    rec.st = SNAPPY_ST_OK;
+    rec.c0 = pos + 8 + bias;
+    rec.clen = len - 4;
+    // (k4_body writes the record's bytes at out + out_off and its status at status[record])
+    uint8_t *const out = edge ? a.slots : a.out;
+    rec.out_off = edge ? (uint64_t)((edge - 1) % a.slot_cap) * SNAPPY_BLOCK : land;
+    rec.want = (uint32_t)(rfl64(a.starts[u + 1]) - rfl64(a.starts[u]));
+    rec.first = a.keys + r;
+    int32_t *const status = reinterpret_cast<int32_t *>(reinterpret_cast<uintptr_t>(a.ustatus) + 4 * p - 4 * (u + 1));
+    k4_body<false, true>(comp, nullptr, 0, 0, SNAPPY_HDR_EVERY_UNIT, 0, 0u, bias, out, status, (uint32_t)(u + 1), rec);
 }
 #endif
 // ---------------------------------------------------------------------------

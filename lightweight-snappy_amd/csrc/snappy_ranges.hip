@@ -135,9 +135,14 @@ __global__ __launch_bounds__(256) void kr7_range_status(const unsigned long long
 
 uint32_t blocks_of(uint64_t items, uint32_t per) { return (uint32_t)((items + per - 1) / per); }
 
+}  // namespace
+
+// ---- shared with the framed form (snappy_frame_ranges.hip; declared in snappy_kernels.h)
+namespace snappy_amd {
+
 // the staging slots of a call: SNAPPY_RANGES_SLOT_CAP, or fewer through the
 // test-only SNAPPY_AMD_RANGE_SLOTS (the reuse path without 64 MiB of edge units)
-uint32_t slot_cap()
+uint32_t ranges_slot_cap()
 {
     const char *e = getenv("SNAPPY_AMD_RANGE_SLOTS");
     if (e && *e) {
@@ -147,7 +152,19 @@ uint32_t slot_cap()
     return SNAPPY_RANGES_SLOT_CAP;
 }
 
-}  // namespace
+void ranges_launch_clip(hipStream_t stream, const snappy_range_unit *plan, uint64_t first, uint32_t units,
+                        const unsigned long long *keys, const uint8_t *slots, uint32_t slot_cap, uint8_t *out)
+{
+    hipLaunchKernelGGL(kr6_clip, dim3(units), dim3(256), 0, stream, plan, first, keys, slots, slot_cap, out);
+}
+
+void ranges_launch_status(hipStream_t stream, const unsigned long long *keys, uint64_t count, int32_t *status,
+                          unsigned long long *first)
+{
+    hipLaunchKernelGGL(kr7_range_status, dim3(blocks_of(count, 256)), dim3(256), 0, stream, keys, count, status, first);
+}
+
+}  // namespace snappy_amd
 
 extern "C" int snappy_amd_decompress_ranges_device(snappy_amd_ctx *c, const void *d_comp, uint64_t comp_origin,
                                                    size_t comp_bytes, const uint64_t *d_offsets, size_t n,
@@ -201,7 +218,7 @@ extern "C" int snappy_amd_decompress_ranges_device(snappy_amd_ctx *c, const void
     for (size_t i = 0; i < count; i++) hkeys[i] = hst[i] == SNAPPY_AMD_OK ? ~0ull : (uint64_t)-hst[i];
     free(hst);
 
-    const uint32_t cap = slot_cap();
+    const uint32_t cap = ranges_slot_cap();
     const uint32_t slots_used = (uint32_t)(nedges < cap ? nedges : cap);
     if ((rc = grow(reinterpret_cast<void **>(&c->r_meta), &c->r_meta_cap, bytes))) return rc;
     // (+ 16: the clip's funnel shift reads the aligned dword after a slot's last byte)
@@ -242,13 +259,12 @@ extern "C" int snappy_amd_decompress_ranges_device(snappy_amd_ctx *c, const void
             a.first = p0;
             hipLaunchKernelGGL(kr4_decode_range_units, dim3((uint32_t)(p1 - p0)), dim3(64), 0, c->stream, a);
             if (edges)
-                hipLaunchKernelGGL(kr6_clip, dim3((uint32_t)(p1 - p0)), dim3(256), 0, c->stream, plan, (uint64_t)p0,
-                                   keys, c->f_scr, cap, static_cast<uint8_t *>(d_out));
+                ranges_launch_clip(c->stream, plan, (uint64_t)p0, (uint32_t)(p1 - p0), keys, c->f_scr, cap,
+                                   static_cast<uint8_t *>(d_out));
             p0 = p1;
         }
     }
-    hipLaunchKernelGGL(kr7_range_status, dim3(blocks_of(count, 256)), dim3(256), 0, c->stream, keys, (uint64_t)count,
-                       d_status, first);
+    ranges_launch_status(c->stream, keys, (uint64_t)count, d_status, first);
     HIP_OK(hipGetLastError());
     if (!sync) return SNAPPY_AMD_OK;
     HIP_OK(hipMemcpyAsync(c->h_total, first, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

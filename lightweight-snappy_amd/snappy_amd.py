@@ -183,6 +183,17 @@ _SIGS = {
     "snappy_decompress_range_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_uint64,
                                                   _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "snappy_decompress_file_range": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p]),
+    # range decode of framed streams
+    "snappy_amd_frame_seek_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                _c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "snappy_frame_tables": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                       _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_uint64)]),
+    "snappy_amd_decompress_frame_ranges_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_size_t,
+                                                             _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                             _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "snappy_decompress_frame_range_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_uint64, _c.c_size_t,
+                                                        _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "snappy_decompress_file_frame_range": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p]),
     "snappy_compress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_void_p]),
     "snappy_decompress_file_framed": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     # Hadoop / snappy-java containers
@@ -400,6 +411,31 @@ def decompress_frame(data, cap: Optional[int] = None) -> bytes:
     out = ctypes.create_string_buffer(max(cap, 1))
     got = ctypes.c_size_t(0)
     _check(lib().snappy_decompress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "decompress_frame")
+    return out.raw[: got.value]
+
+
+def frame_tables(data):
+    """(chunk table, seek table, decoded bytes) of a framed stream: the chunk walk
+    on the host, no kernel.  Both tables are lists of data chunks + 1 entries."""
+    p, n, keep = _buf(data)
+    room = n // 8 + 2  # (a stream holds at most one data chunk per 8 bytes)
+    chunks, starts = (ctypes.c_uint64 * room)(), (ctypes.c_uint64 * room)()
+    nch, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    _check(lib().snappy_frame_tables(p, n, chunks, starts, room, ctypes.byref(nch), ctypes.byref(total)), "frame_tables")
+    return list(chunks[: nch.value + 1]), list(starts[: nch.value + 1]), total.value
+
+
+def decompress_frame_range(data, start: int, length: int) -> bytes:
+    """Bytes [start, start + length) of decompress_frame(data), CRC-checked: the
+    chunk headers are walked on the host up to the range's last chunk and only the
+    chunks the range touches are uploaded."""
+    p, n, keep = _buf(data)
+    if start < 0 or length < 0:
+        raise SnappyError(ERR_ARG, "decompress_frame_range")
+    out = ctypes.create_string_buffer(max(length, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_decompress_frame_range_buffer(p, n, start, length, out, length, ctypes.byref(got)),
+           "decompress_frame_range")
     return out.raw[: got.value]
 
 
@@ -769,6 +805,52 @@ class Codec:
                                                         ctypes.c_void_p(out.data_ptr()), n, ctypes.byref(got)),
                "decompress_frame_device")
         return out[: got.value]
+
+    def frame_seek_tensor(self, frame, chunks):
+        """Seek table of a framed stream in HBM from its chunk table (int64 CUDA
+        tensor, data chunks + 1 entries) -> (decoded bytes, int64 CUDA tensor of
+        as many entries: each data chunk's decoded position, then the total)."""
+        assert frame.is_cuda and frame.dtype == torch.uint8 and frame.is_contiguous()
+        assert chunks.is_cuda and chunks.dtype == torch.int64 and chunks.is_contiguous() and chunks.numel() >= 1
+        starts = torch.empty(chunks.numel(), dtype=torch.int64, device=frame.device)
+        n = ctypes.c_size_t(0)
+        self._bind_stream()
+        _check(lib().snappy_amd_frame_seek_device(self._h, ctypes.c_void_p(frame.data_ptr()), frame.numel(),
+                                                  ctypes.c_void_p(chunks.data_ptr()), chunks.numel() - 1,
+                                                  ctypes.c_void_p(starts.data_ptr()), ctypes.byref(n)),
+               "frame_seek_device")
+        return n.value, starts
+
+    def decompress_frame_ranges_tensor(self, window, comp_origin: int, chunks, starts, ranges, out=None):
+        """Decode the byte ranges `ranges` -- a list or array of (start, length,
+        out_offset) -- of the framed stream whose bytes [comp_origin, comp_origin +
+        window.numel()) are `window`, through its chunk table and seek table (or
+        equally long contiguous sub-tables of both; int64 CUDA tensors).  Range i
+        lands at out[out_offset_i : out_offset_i + length_i]; out=None allocates
+        max(out_offset + length) bytes.  Returns (out, status): an int32 CUDA tensor
+        of each range's status (self.last_ranges_status = the first failure)."""
+        import numpy as np
+        assert window.is_cuda and window.dtype == torch.uint8 and window.is_contiguous()
+        for t in (chunks, starts):
+            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+        assert chunks.numel() == starts.numel() >= 1
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 3))
+        count = r.shape[0]
+        if out is None:
+            need = int((r[:, 1] + r[:, 2]).max()) if count else 0
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=window.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=window.device)
+        self._bind_stream()
+        rc = lib().snappy_amd_decompress_frame_ranges_device(
+            self._h, ctypes.c_void_p(window.data_ptr()), comp_origin, window.numel(),
+            ctypes.c_void_p(chunks.data_ptr()), ctypes.c_void_p(starts.data_ptr()), chunks.numel() - 1,
+            r.ctypes.data_as(ctypes.c_void_p), count, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(status.data_ptr()))
+        self.last_ranges_status = rc
+        if rc == ERR_DEVICE or (rc == ERR_ARG and not count):
+            raise SnappyError(rc, "decompress_frame_ranges_device")
+        return out, status[:count]
 
     # Hadoop / snappy-java containers -------------------------------------------
     def compress_container_tensor(self, x, format, block: int = 0, flags: int = 0, out=None, tables: bool = True):
