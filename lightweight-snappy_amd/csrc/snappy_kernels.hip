@@ -93,9 +93,16 @@ __device__ __forceinline__ uint32_t skipsum(uint32_t m)
 // ---------------------------------------------------------------------------
 // K1r: register-resident match finder (one wave per unit).
 //
-//  * The unit lives in VGPRs: register r, lane l holds big-endian dword
-//    64 r + l (128 VGPRs v2..v129 hold 32 KiB).  65,536-byte blocks keep a
-//    ring of their last 128 256-byte segments there instead (segment s in
+//  * The unit lives in VGPRs: register r, lane l holds dword 64 r + l as it
+//    lies in memory (little-endian: byte 4 d of the unit is the low byte of
+//    dword d; 128 VGPRs v2..v129 hold 32 KiB).  The four bytes at any position
+//    x are then ({dword x / 4 + 1, dword x / 4} >> 8 (x & 3)): one
+//    v_alignbyte_b32 with x itself as the shift operand (it reads S2[1:0]
+//    alone, tools/micro/alignbyte.hip), and the first differing byte of two
+//    such values is the lowest set byte of their xor (v_ffbl_b32).  Only the
+//    hash wants the big-endian value: one byte swap per window lane.
+//    65,536-byte blocks keep a ring of their last 128 256-byte segments in
+//    the registers instead (segment s in
 //    register s % 128, loaded ahead of the probe window; measured on the text
 //    workload only 1.4 % of candidate checks reach further back, and those read
 //    global memory), so both kernels run 3 waves per SIMD.  A wave-uniform
@@ -107,7 +114,8 @@ __device__ __forceinline__ uint32_t skipsum(uint32_t m)
 //    without touching the input; equal tags are verified against the bytes,
 //    so the probe/insert sequence of src/snappy_compression.c:384-403 is
 //    reproduced bit for bit.
-//  * Position window: lane l <-> position q0 + l holds the BE32 there (`bv`),
+//  * Position window: lane l <-> position q0 + l holds the BE32 there (`bv`,
+//    the funnelled bytes swapped once for the hash),
 //    its hash and tag (`hv`), the nearest earlier window lane with the same
 //    hash (DPP wave_shr chain, up to DMAX back) and the table entry of its
 //    slot (`ent`, re-read after every round's inserts).
@@ -201,7 +209,7 @@ constexpr uint32_t kRegs = 128;  // VGPRs holding a 32 KiB unit (64 dwords each)
         }                                                                                            \
     } while (0)
 
-// lane i <- big-endian dword d + i of the unit (d wave-uniform): registers
+// lane i <- dword d + i of the unit (d wave-uniform): registers
 // R = d / 64 and R + 1 merged at lane d % 64 hold the 64 dwords rotated by
 // d % 64; one ds_bpermute puts them in order (it reads lane addr[7:2], so
 // the rotation needs no masking: tools/micro/lds_packed3.hip)
@@ -228,12 +236,12 @@ __device__ __forceinline__ uint32_t wave_shr1(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
 }
 
-// big-endian funnel by bytes: the 32 bits starting k bytes (0..3) into the
-// 64-bit big-endian hi:lo, one v_perm_b32 (selector bytes 4-k..7-k)
-__device__ __forceinline__ uint32_t perm_sel(uint32_t k) { return 0x07060504u - k * 0x01010101u; }
-__device__ __forceinline__ uint32_t funnel_bytes(uint32_t hi, uint32_t lo, uint32_t sel)
+// the four bytes at position x (as they lie in memory) from the dword that
+// holds x (`cur`) and the one after it (`next`): one v_alignbyte_b32, which
+// shifts by x's low two bits alone
+__device__ __forceinline__ uint32_t bytes_at(uint32_t cur, uint32_t next, uint32_t x)
 {
-    return __builtin_amdgcn_perm(hi, lo, sel);
+    return __builtin_amdgcn_alignbyte(next, cur, x);
 }
 
 // The nearest lane l - d (1 <= d <= D) whose word has the same upper half as
@@ -514,10 +522,10 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     (void)t_start;
 #endif
 
-    // unit -> registers, big-endian dwords, zero past the end
+    // unit -> registers, dwords in memory order, zero past the end
     v32 g0, g1, g2, g3;
     const bool aligned = ((reinterpret_cast<uintptr_t>(src) & 3) == 0);
-    // big-endian dword k (per lane) of the unit, zero past its end
+    // dword k (per lane) of the unit, zero past its end
     auto load_dw = [&](uint32_t k) -> uint32_t {
         const uint32_t b = 4 * k;
         uint32_t w = 0;
@@ -527,7 +535,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             for (uint32_t k = 0; k < 4; k++)
                 if (b + k < L) w |= (uint32_t)src[b + k] << (8 * k);
         }
-        return __builtin_bswap32(w);
+        return w;
     };
     auto load_word = [&](uint32_t i) -> uint32_t { return load_dw(64 * i + lane); };
 #pragma unroll
@@ -585,7 +593,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
                 uint32_t w;
                 asm volatile("v_lshl_add_u32 %0, %1, 2, %2\n\tds_read_b32 %0, %0\n\ts_waitcnt lgkmcnt(0)"
                              : "=&v"(w) : "v"(lane), "s"(lds) : "memory");
-                REG_SET_V(sg & (kRegs - 1), __builtin_bswap32(w));
+                REG_SET_V(sg & (kRegs - 1), w);
                 sg++;
             }
             for (; sg < need; sg++) {
@@ -596,7 +604,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             if (decltype(pf)::value) stage(seg_hi);  // REG_SET_V consumed the LDS read: the DMA may overwrite it
         }
     };
-    // lane i <- big-endian dword dd + i: from the registers, or (BIG, a segment
+    // lane i <- dword dd + i: from the registers, or (BIG, a segment
     // that left the ring) from global memory
 #define CAND_LANES(dd)                                                                             \
     ({                                                                                             \
@@ -617,7 +625,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 
     // never-set slots mean position 0 (snappy_compression.c:259-265): tag of BE32(0)
     const uint32_t cur0 = __builtin_amdgcn_readfirstlane(REG_OF(0));
-    const uint32_t init = TAG_OF(cur0) << 16;
+    const uint32_t init = TAG_OF(__builtin_bswap32(cur0)) << 16;
     for (uint32_t i = lane; i < kTable; i += 64) TBL_WRITE(i, init);
     __syncthreads();
 
@@ -673,11 +681,14 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     uint32_t pdnz = 0;  // the predecessor's tag
     uint64_t m_win = 0, m_win17 = 0;
     bool lsw = false;  // the lane-space data describe the current window
-// 32 KiB units take a window's per-lane BE32 by v_alignbit from (p - 1) / 4
-// (as the round loop's pa funnel, V6); K1r64 keeps v_perm with a per-lane
-// selector from a 32-bit multiply (A/B, outputs identical, profiles/r05zj_*:
-// 32 KiB streams 12.64 -> 12.55-12.57 ms per GiB, but 64 KiB blocks
-// 14.06 -> 14.41 in K1r64's schedule)
+// A window lane's BE32 for the hash: the dword that holds q0 + lane and the one
+// after it through one v_perm_b32 whose per-lane selector funnels and swaps at
+// once (bytes k .. k + 3 of the pair, the first one highest: 0x00010203 + k *
+// 0x01010101, made while the gathers are in flight).  v_alignbyte and a swap
+// behind it, the asm refresh's form, is one more instruction on the chain from
+// the gathers to the hash: K1r64 on random blocks, whose W-probe rounds move
+// the window every round or two, measured 3.97-4.00 -> 4.03-4.05 ms per GiB
+// with it (profiles/r16h_per_gib_random_alignbyte_form.log).
 #define WINDOW_AT(qq)                                                                             \
     do {                                                                                           \
         q0 = (qq);                                                                                 \
@@ -689,19 +700,12 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             REG_PAIR(d0 >> 6, _r0, _r1);                                                           \
             dv = lane >= dr ? _r0 : _r1;                                                           \
         }                                                                                          \
-        if (!BIG) {                                                                                \
-            /* the dwords from (p - 1) / 4 funnelled by v_alignbit with the lane's */              \
-            /* shift -8 p (bits 4:0; 0 takes the second dword, the one at p) */                    \
-            const uint32_t _p = q0 + lane;                                                          \
-            const uint32_t _k = (_p - 1) >> 2; /* rotated by dr = d0 % 64 */                       \
+        {                                                                                          \
+            const uint32_t _p = q0 + lane;                                                         \
+            const uint32_t _k = _p >> 2; /* rotated by dr = d0 % 64 */                             \
             const uint32_t _a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(_k << 2), (int)dv);   \
             const uint32_t _b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((_k + 1) << 2), (int)dv); \
-            bv = __builtin_amdgcn_alignbit(_a, _b, 0u - (_p << 3));                                  \
-        } else {                                                                                   \
-            const uint32_t _k = d0 + (((q0 & 3) + lane) >> 2); /* rotated by dr = d0 % 64 */     \
-            const uint32_t _a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(_k << 2), (int)dv);   \
-            const uint32_t _b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((_k + 1) << 2), (int)dv); \
-            bv = funnel_bytes(_a, _b, perm_sel((q0 + lane) & 3));                                 \
+            bv = __builtin_amdgcn_perm(_b, _a, 0x00010203u + (_p & 3) * 0x01010101u);              \
         }                                                                                          \
         {                                                                                          \
             const uint32_t _pr = bv * kMul;                                                        \
@@ -744,13 +748,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
                 const uint32_t qa = pf + len, qb = cand + len;
                 ring_to((qa >> 8) + 2, std::false_type{});
                 const uint32_t a0 = DW_LANES(qa >> 2), b0 = CAND_LANES(qb >> 2);
-                const uint32_t va = funnel_bytes(a0, wave_shl1(a0), perm_sel(qa & 3));
-                const uint32_t vb = funnel_bytes(b0, wave_shl1(b0), perm_sel(qb & 3));
+                const uint32_t va = bytes_at(a0, wave_shl1(a0), qa);
+                const uint32_t vb = bytes_at(b0, wave_shl1(b0), qb);
                 const uint32_t yy = lane < 63 ? (va ^ vb) : 0;  // lane 63 lacks its successor
                 const uint64_t bb = __ballot(yy != 0);
                 if (bb) {
                     const uint32_t m = (uint32_t)__builtin_ctzll(bb);
-                    len += 4 * m + ((uint32_t)__builtin_clz(__builtin_amdgcn_readlane(yy, m)) >> 3);
+                    len += 4 * m + ((uint32_t)__builtin_ctz(__builtin_amdgcn_readlane(yy, m)) >> 3);
                     break;
                 }
                 len += 252;
@@ -760,13 +764,13 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     auto match_len = [&](uint32_t pf, uint32_t cand) -> uint32_t {
         const uint32_t pa = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((pf >> 2) + lane) << 2), (int)dv);
         const uint32_t ca = CAND_LANES(cand >> 2);
-        const uint32_t pv = funnel_bytes(pa, wave_shl1(pa), perm_sel(pf & 3));
-        const uint32_t cv = funnel_bytes(ca, wave_shl1(ca), perm_sel(cand & 3));
+        const uint32_t pv = bytes_at(pa, wave_shl1(pa), pf);
+        const uint32_t cv = bytes_at(ca, wave_shl1(ca), cand);
         const uint32_t y = pv ^ cv;
         const uint64_t bad = __ballot(y != 0) & 0xFFFFull;
         if (bad) {
             const uint32_t m = (uint32_t)__builtin_ctzll(bad);
-            return 4 * m + ((uint32_t)__builtin_clz(__builtin_amdgcn_readlane(y, m)) >> 3);
+            return 4 * m + ((uint32_t)__builtin_ctz(__builtin_amdgcn_readlane(y, m)) >> 3);
         }
         return match_len_from(pf, cand, 64);
     };
@@ -855,14 +859,16 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 //    predecessor's tag, V16); a lane past the window has bit 24 of its
 //    word set, so it never matches (V6); the hit branch on the SCC of the s_and
 //    that makes the hit mask (V2)
-//  * pa: the dwords at pf gathered from (pf - 1) / 4 and funnelled by v_alignbit
-//    with the shift -8 pf from v_mul_i32_i24 (bits 4:0; 0 takes the second
-//    dword, the one at pf) (V6, V10)
+//  * pa: the dwords at pf gathered from pf / 4 and funnelled with each lane's
+//    successor (wave_shl:1) by v_alignbyte_b32, pf itself the shift operand; ca
+//    the same with c.  (While the registers held big-endian dwords, pa came from
+//    (pf - 1) / 4 through v_alignbit with a v_mul_i32_i24 shift, V6 / V10, and ca
+//    through v_perm_b32 with a selector made by three scalar instructions.)
 //  * ca: the candidate's register pair R, R + 1 selected by one v_cndmask with
 //    s_set_gpr_idx on SRC0 and SRC1 (lanes >= l0 take R; V15); K1r64 reads ring
 //    registers (c / 256) mod 128: a candidate whose segment left the ring is
-//    gathered from the input (global_load_dword, byte-swapped to the ring's
-//    big-endian dwords; V19), the wrap pair 127 / 0 by a select of v129 / v2
+//    gathered from the input (global_load_dword: memory order, as the ring's
+//    dwords; V19), the wrap pair 127 / 0 by a select of v129 / v2
 //    without a register index (round 6; it left for the C++ round before:
 //    64 KiB blocks 14.11 -> 14.14-14.18 ms per GiB unpinned, within the loop
 //    placement's +-2 %, profiles/r06e_ab_*)
@@ -873,7 +879,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 //    mask from one s_bfm_b64 (at most DMAX + 1 lanes, so the 6-bit size never
 //    wraps; no dummy-record writes: V13) and the next round's entry reads issued
 //    after it, behind the funnels (V18)
-//  * the prefix length per lane as (clz(xor) >> 3) | 4 lane, read back from the
+//  * the prefix length per lane as (ctz(xor) >> 3) | 4 lane, read back from the
 //    first differing dword (V3, V7); skip is not reset by a hit round (a pending
 //    token implies skip 32, V8); the clamp to the block end only on the exit path
 // Each masked insert restores exec to its value where the statement runs (sx,
@@ -976,7 +982,7 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "s_ff1_i32_b64 %[f], %[hm]\n\t"                                                         \
             "v_readlane_b32 %[c], %[t1], %[f]\n\t"                                                  \
             "s_add_u32 %[pf], %[q0], %[f]\n\t"                                                      \
-            "v_add3_u32 %[t2], %[pf], -1, %[lane4]\n\t" /* dwords from (pf - 1) / 4 */              \
+            "v_add_u32_e32 %[t2], %[pf], %[lane4]\n\t" /* dwords from pf / 4 */                     \
             "ds_bpermute_b32 %[t2], %[t2], %[dv]\n\t" /* pa: dwords at pf */                        \
             CAND                                                                                    \
             "s_bfe_u32 %[s1], %[c], 0x60002\n\t"                                                    \
@@ -991,21 +997,17 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
             "s_sub_u32 %[dkb], %[pf], %[c]\n\t" /* this round's token offset */                     \
             "s_cmp_lt_u32 %[lane0], %[f]\n\t"                                                       \
             "s_subb_u32 %[s0], %[lane0], 0\n\t" /* lo0 */                                           \
-            "v_mul_i32_i24_e64 %[t0], %[pf], -8\n\t" /* pa's funnel shift */                        \
             "s_sub_u32 %[s2], %[f], %[s0]\n\t"                                                      \
             "s_add_u32 %[s2], %[s2], 1\n\t" /* lanes lo0 .. f insert */                             \
-            "s_and_b32 %[s3], %[c], 3\n\t"                                                          \
-            "s_mul_i32 %[s3], %[s3], 0xfefefeff\n\t"                                                \
-            "s_add_i32 %[s3], %[s3], 0x7060504\n\t" /* ca's perm selector */                        \
             "s_waitcnt lgkmcnt(0)\n\t" /* pa and ca */                                               \
             "v_mov_b32_dpp %[t1], %[t2] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"     \
             "v_mov_b32_dpp %[t4], %[t3] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"     \
-            "v_alignbit_b32 %[t2], %[t2], %[t1], %[t0]\n\t"                                         \
-            "v_perm_b32 %[t3], %[t3], %[t4], %[s3]\n\t"                                             \
+            "v_alignbyte_b32 %[t2], %[t1], %[t2], %[pf]\n\t" /* the bytes at pf + 4 lane: {next, own} >> 8 (pf & 3) */ \
+            "v_alignbyte_b32 %[t3], %[t4], %[t3], %[c]\n\t"  /* and at c + 4 lane */                \
             K1R_INSERTS("%[s2]", "%[s0]")                                                           \
             "v_cmp_ne_u32_e32 vcc, %[t2], %[t3]\n\t"                                                \
             "v_xor_b32_e32 %[t2], %[t2], %[t3]\n\t"                                                 \
-            "v_ffbh_u32_e32 %[t2], %[t2]\n\t"                                                       \
+            "v_ffbl_b32_e32 %[t2], %[t2]\n\t" /* memory order: the first differing byte is the lowest */ \
             "v_bfe_u32 %[t2], %[t2], 3, 2\n\t"                                                      \
             "v_lshl_or_b32 %[t2], %[lane], 2, %[t2]\n\t" /* the prefix length if this dword differs */ \
             "s_ff1_i32_b32 %[s1], vcc_lo\n\t"                                                       \
@@ -1061,10 +1063,11 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
 // K1R_WIN_PATH: K1r's window refresh as a path of the statement (_win)
 // instead of a code-2 exit, the C++ WINDOW_LS and a re-entry, when no token
 // flush is due (pend + dkn <= 48: 444 of a 32 KiB text unit's 518 refreshes).
-// It is WINDOW_LS(p - 1) for !BIG (the v_alignbit form), instruction for
-// instruction the compiler's own schedule of it: the register pair of q0 / 256
-// under s_set_gpr_idx_on, two ds_bpermute and v_alignbit for each lane's BE32,
-// the kMul hash with its tag, the new entries read as soon as their addresses
+// It does what WINDOW_LS(p - 1) does for !BIG, after the compiler's own
+// schedule of it: the register pair of q0 / 256 under s_set_gpr_idx_on, two
+// ds_bpermute, v_alignbyte and the byte swap (v_perm_b32, selector bsw; the
+// C++ has one v_perm_b32 with a per-lane selector) for each lane's BE32, the
+// kMul hash with its tag, the new entries read as soon as their addresses
 // exist, nearest_same_key<13> (every DPP read two states behind the VALU write
 // of its source), the lane data, word with bit 24 on the lanes past the window,
 // m_win and lim0; then lane0 = 1 and the skip test the statement's entry makes.
@@ -1255,10 +1258,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_set_gpr_idx_off\n\t"                                                                         \
     "v_cmp_gt_u32_e32 vcc, %[s1], %[lane]\n\t" /* lanes < dr take register R + 1 */                 \
     "v_add_u32_e32 %[t2], %[q0], %[lane]\n\t"                                                       \
-    "v_mul_i32_i24_e64 %[t3], %[t2], -8\n\t" /* the funnel shift, as pa's */                        \
-    "v_add_u32_e32 %[t4], -1, %[t2]\n\t"                                                            \
-    "v_cndmask_b32_e32 %[dv], %[t0], %[t1], vcc\n\t"                                                \
-    "v_and_b32_e32 %[t4], -4, %[t4]\n\t" /* dwords from (p - 1) / 4 */                              \
+    "v_and_b32_e32 %[t4], -4, %[t2]\n\t" /* the dword that holds q0 + lane, and the next */        \
+    "v_cndmask_b32_e32 %[dv], %[t0], %[t1], vcc\n\t" /* (two states behind the compare) */          \
     "ds_bpermute_b32 %[t0], %[t4], %[dv]\n\t"                                                       \
     "ds_bpermute_b32 %[t1], %[t4], %[dv] offset:4\n\t"                                              \
     "s_mov_b32 %[s0], 0xffff0000\n\t"                                                               \
@@ -1269,7 +1270,8 @@ __device__ __forceinline__ void k1r_body(const uint8_t *__restrict__ in, uint64_
     "s_mov_b32 %[lane0], 1\n\t"                                                                     \
     "v_mov_b32_e32 %[pdl1], 0x100\n\t"                                                              \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                      \
-    "v_alignbit_b32 %[t0], %[t0], %[t1], %[t3]\n\t" /* BE32 at q0 + lane */                         \
+    "v_alignbyte_b32 %[t0], %[t1], %[t0], %[t2]\n\t" /* the bytes at q0 + lane */                   \
+    "v_perm_b32 %[t0], %[t0], %[t0], %[bsw]\n\t" /* their BE32, for the hash alone */               \
     "v_mul_lo_u32 %[t0], %[t0], %[kmul]\n\t"                                                        \
     "v_lshrrev_b32_e32 %[adrt], %[shift], %[t0]\n\t" /* the slot */                                 \
     "v_bfe_u32 %[t3], %[t0], %[sh8], 8\n\t" /* the tag */                                           \
@@ -1319,6 +1321,7 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
       [nt] "+s"(nt), [acc] "+s"(acc), [cend] "+s"(cend) /* the flush */
 #define K1R_WINOPS_PATH_IN(SEGHI)                                                                   \
     [L] "s"(L), [lm16] "s"(L - 16), [seghi] SEGHI, [shift] "s"(shift), [sh8] "s"(shift - 8), [kmul] "s"(kMul),    \
+    [bsw] "s"(0x00010203u), /* v_perm_b32 selector: the byte swap in front of the hash */           \
     [tokb] "s"(tok), [segb] "s"(segu), /* the flush */
 #define K1R_ASM_ROUNDS_STMT(code, fx, cx, e32, et32, CAND, SEGHI, PAD, DUAL_SEL, DUAL_LOOP, WIN, WIN_OUT, WIN_IN, X5, LEAVE) \
     do {                                                                                            \
@@ -1340,10 +1343,8 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
             "L%=_far:\n\t" /* K1r64: the candidate's 256 bytes from the input */                    \
             "s_and_b32 %[s1], %[c], -4\n\t"                                                         \
             "v_add_u32_e32 %[t1], %[s1], %[lane4]\n\t"                                              \
-            "global_load_dword %[t3], %[t1], %[srcb]\n\t"                                           \
-            "s_mov_b32 %[s1], 0x10203\n\t"                                                          \
+            "global_load_dword %[t3], %[t1], %[srcb]\n\t" /* memory order, as the ring registers */ \
             "s_waitcnt vmcnt(0)\n\t"                                                                \
-            "v_perm_b32 %[t3], %[t3], %[t3], %[s1]\n\t" /* big-endian, as the ring registers */    \
             "s_branch L%=_farret\n"                                                                 \
             "L%=_wrap:\n\t" /* K1r64: registers 127 (v129, lanes >= l0) and 0 (v2) */               \
             "s_bfe_u32 %[s1], %[c], 0x60002\n\t"                                                    \
@@ -1585,12 +1586,12 @@ static_assert(kK2Seg == 256, "K1R_FLUSH_PATH: one segment record per flush at mo
                     TBL_READ_ENT(adr);  // the next round's entries, in flight during the verification
                     LSTAMP(s2);
                     LSEG(1, s1, s2);
-                    const uint32_t pv = funnel_bytes(pa, wave_shl1(pa), perm_sel(pf & 3));
-                    const uint32_t cv = funnel_bytes(ca, wave_shl1(ca), perm_sel(c & 3));
+                    const uint32_t pv = bytes_at(pa, wave_shl1(pa), pf);
+                    const uint32_t cv = bytes_at(ca, wave_shl1(ca), c);
                     const uint32_t y = pv ^ cv;
                     const uint64_t bad = __ballot(y != 0) & 0xFFFFull;
                     // per lane: the prefix length if its dword holds the first mismatch
-                    const uint32_t lenv = 4 * lane + ((uint32_t)__builtin_clz(y | 1) >> 3);
+                    const uint32_t lenv = 4 * lane + ((uint32_t)__builtin_ctz(y | 0x80000000u) >> 3);
                     // read before the test: with bad == 0 the lane index is garbage and len is replaced
                     uint32_t len = __builtin_amdgcn_readlane(lenv, (uint32_t)__builtin_ctzll(bad) & 63);
                     if (__builtin_expect(bad == 0, 0)) len = match_len_from(pf, c, 64);
