@@ -730,6 +730,105 @@ int snappy_compress_file_container(FILE *file_input, unsigned long long input_si
                                    FILE *file_compressed);
 int snappy_decompress_file_container(FILE *file_input, int format, FILE *file_decompressed);
 
+/* ---- range decode of a container: through its chunk tables --------------- */
+/* Random access into a Hadoop or snappy-java container.  Every chunk is one raw
+ * stream of its own, so any chunk decodes alone (ERR_DEPENDENT cannot happen);
+ * the chunk tables say where every payload is, so the format is not an argument.
+ *
+ * d_window[0, comp_bytes) holds the container's bytes [comp_origin, comp_origin +
+ * comp_bytes): the resident window.  d_comp_off_len and d_out_off_len (device)
+ * are nchunks pairs each: the chunk tables of container_index_device or
+ * compress_container_device, or any contiguous run of their pairs; offsets stay
+ * absolute.  The decoded extent they cover is [off[0], off[nchunks - 1] +
+ * len[nchunks - 1]) of d_out_off_len.  Range i (host memory) writes the decoded
+ * bytes [start, start + length) to d_out[out_offset, out_offset + length); length
+ * == 0 is OK and touches nothing.  The call is synchronous: the tables are in HBM,
+ * so the plan (csrc/snappy_container_ranges.h) runs there and 64 bytes are read
+ * back to size this call's launches; the long-record decode underneath reads 64
+ * bytes of its own per launch group, and a call whose edge chunks exceed the
+ * staging budget reads 8 bytes per launch group once more.
+ *
+ * A range's span: its first chunk u0 is the last i with off[i] <= start, its last
+ * chunk u1 the last i with off[i] <= start + length - 1, both by binary search
+ * over d_out_off_len.  Every chunk u0..u1 is one decode unit, decoded whole as one
+ * record of decompress_long_records_device (a chunk of more than 65,536 bytes gets
+ * its block table from that call's per-record walk, and both decode passes run);
+ * an empty chunk inside the span is skipped (not read, no effect on the status).
+ * A chunk that lies wholly inside its range decodes straight into d_out; an edge
+ * chunk (at most two per range) decodes whole into staging in context scratch and
+ * its wanted part is copied out.  A chunk that several ranges share is decoded
+ * once per range.
+ *
+ * Staging: the budget is 1,024 x 65,536 bytes (64 MiB; SNAPPY_AMD_RANGE_SLOTS x
+ * 65,536 where that is set).  Edge chunks stand at 16-byte-aligned places, in plan
+ * order; one that does not fit behind those before it opens the next launch
+ * group, which reuses the area.  An edge chunk larger than the budget is a group
+ * of its own.  Scratch: a call grows snappy_amd_device_bytes() by at most
+ *   max(budget, the largest edge chunk rounded up to 16) + 16 of staging,
+ *   + snappy_amd_max_long_records_scratch(T, U) for the derived batch of the
+ *     largest launch group (T decoded bytes in U units; at most all units),
+ *   + 68 bytes per unit and 100 per range, + 88,
+ *   each of the three buffers with grow()'s slack: an eighth and a page.
+ *
+ * d_status (count i32, device; may be NULL) gets every range's status; the call
+ * returns the first failing range's.  In this order:
+ *   ERR_ARG        the range leaves the tables' decoded extent, or nchunks == 0
+ *                  with length > 0
+ *   ERR_CAPACITY   the output range leaves [0, out_bytes)
+ *   ERR_INDEX      the search gives u1 < u0 (a table that is not sorted)
+ *  then the table stage, over every non-empty unit before anything is decoded; a
+ *  range with a failing unit decodes and stores nothing, and its status is its
+ *  lowest failing chunk's, for each chunk the first of:
+ *   ERR_TRUNCATED  the payload [comp_off, comp_off + comp_len) is not inside the
+ *                  window
+ *   ERR_HEADER     comp_len == 0
+ *   ERR_UNSUPPORTED  a decoded length above 2^30
+ *   ERR_INDEX      the tables contradict themselves about the unit: a chunk inside
+ *                  the span that begins before the range or ends after it, or does
+ *                  not end where the next one begins; an empty first or last chunk
+ *   ERR_HEADER     a preamble that does not end inside the payload's first five
+ *                  bytes, or is not the table's length
+ *  then the decode: element errors of the long-record decode, the lowest failing
+ *  chunk of the range.
+ * Guarantees: no byte of d_out outside the accepted ranges' output is written,
+ * whatever the tables say (a range that fails while it decodes may leave part of
+ * its own output written); a refused or failing range never disturbs another; no
+ * read leaves the window, except within the aligned dword that holds its first
+ * byte.  For a sorted, contiguous table a range's status is what
+ * decompress_container_device (tables given) returns for exactly that range's
+ * non-empty chunks, when at most one of them fails (of two failing chunks this
+ * call names the lower one; that call names a table failure before a decode
+ * failure).  What success proves: each touched chunk agrees with its table
+ * entries.  It does not prove that the tables are the container's -- that stays
+ * the caller's word. */
+int snappy_amd_decompress_container_ranges_device(snappy_amd_ctx *ctx, const void *d_window, uint64_t comp_origin,
+                                                  size_t comp_bytes, const uint64_t *d_comp_off_len,
+                                                  const uint64_t *d_out_off_len, size_t nchunks,
+                                                  const snappy_amd_range *ranges, size_t count, void *d_out,
+                                                  size_t out_bytes, int32_t *d_status);
+/* The chunk tables of a container in host memory: the host walk, no kernel, the
+ * same rules as container_index_device.  Room for max_chunks pairs each; either
+ * table may be NULL.  *nchunks_out = the chunks, *len = the decoded bytes; more
+ * chunks than max_chunks is SNAPPY_AMD_ERR_CAPACITY, with *nchunks_out the pairs
+ * needed. */
+int snappy_container_tables(const uint8_t *in, size_t n, int format, uint64_t *comp_off_len, uint64_t *out_off_len,
+                            size_t max_chunks, size_t *nchunks_out, uint64_t *len);
+/* Host forms: exactly bytes [start, start + length) of
+ * snappy_decompress_container_buffer's output, or SNAPPY_AMD_ERR_ARG for a range
+ * that leaves it.  Both hop from header to header with the walk's own step, 16
+ * bytes per hop (the FILE* form with positional reads from the current position;
+ * no payload beyond those bytes is read), carrying Hadoop's open block and the
+ * owed snappy-java header, and stop at the chunk holding the range's last byte: a
+ * damaged chunk after it is never seen, one before it is the walk's error, a
+ * stream that ends first is checked as a whole stream's end and is then ERR_ARG.
+ * The window [payload of u0, end of payload of u1) is then read with one seek and
+ * one read and uploaded at its own address residue with the sub-tables.  A
+ * file_input that cannot seek is SNAPPY_AMD_ERR_UNSUPPORTED. */
+int snappy_decompress_container_range_buffer(const uint8_t *in, size_t n, int format, uint64_t start, size_t length,
+                                             uint8_t *out, size_t cap, size_t *out_len);
+int snappy_decompress_file_container_range(FILE *file_input, int format, uint64_t start, uint64_t length,
+                                           FILE *file_out);
+
 /* Kernel timing of the last compress/decompress call, measured with HIP
  * events on the launch stream: K1 (block compress), K3 (scan + gather),
  * K4 (block decode), milliseconds. */

@@ -8,16 +8,24 @@
 // place of the device walk (KC1).  Both follow snappy_container_step
 // (snappy_container.h).  Large inputs go piece by piece: the compressors in
 // pieces that are a multiple of the block, the decoders in runs of whole
-// chunks.  Declared in include/snappy_amd.h.
+// chunks.  The range forms walk only up to the chunk that holds
+// the range's last byte, 16 bytes per hop, and hand the span's payloads and
+// sub-tables to snappy_amd_decompress_container_ranges_device.  Declared in
+// include/snappy_amd.h.
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/types.h>
+#include <unistd.h>
+#include <new>
+#include <stdexcept>
 #include <vector>
 
 #include "snappy_amd.h"
 #include "snappy_container.h"
+#include "snappy_container_ranges.h"
 #include "snappy_ctx.h"
 
 namespace {
@@ -196,6 +204,131 @@ int container_decode_all(snappy_amd_ctx *c, const uint8_t *in, int format, const
     *out_len = at;
     return SNAPPY_AMD_OK;
 }
+
+// ---- range decode ------------------------------------------
+// a container the host can read at any position: host memory, or a file
+// descriptor whose stream starts at `base` (positional reads: the FILE*'s own
+// position and buffer are not touched by the walk)
+struct ContainerSource {
+    uint64_t clen = 0;
+    const uint8_t *mem = nullptr;
+    int fd = -1;
+    off_t base = 0;
+    // x = the window of snappy_container_step at pos: 16 bytes, zero past the stream's end
+    int head(uint64_t pos, uint32_t x[4]) const
+    {
+        uint8_t w[SNAPPY_CONTAINER_WINDOW] = {};
+        const uint64_t avail = clen - pos;
+        const size_t want = avail < SNAPPY_CONTAINER_WINDOW ? (size_t)avail : SNAPPY_CONTAINER_WINDOW;
+        if (mem) {
+            memcpy(w, mem + pos, want);
+        } else {
+            size_t got = 0;
+            while (got < want) {
+                const ssize_t k = pread(fd, w + got, want - got, base + (off_t)(pos + got));
+                if (k <= 0) return SNAPPY_AMD_ERR_IO;
+                got += (size_t)k;
+            }
+        }
+        snappy_container_window(w, want, x);
+        return SNAPPY_AMD_OK;
+    }
+};
+
+// Hop from header to header until `target` decoded bytes are covered (the chunk
+// holding byte target - 1 is the last one looked at) or the stream ends, which is
+// then checked as the whole-stream walk checks it; no payload beyond the step's 16
+// bytes is read.  comp / outp = the tables of the chunks seen; Hadoop's open block
+// and the owed snappy-java header are carried from hop to hop.
+int container_walk_to(const ContainerSource &src, int format, uint64_t target, std::vector<uint64_t> *comp,
+                      std::vector<uint64_t> *outp)
+{
+    WalkState s = {format == SNAPPY_AMD_CONTAINER_XERIAL, 0};
+    uint64_t pos = 0, sum = 0;
+    while (sum < target) {
+        if (pos >= src.clen) return snappy_container_end(format, s.first, s.R);
+        uint32_t x[4], coff, cl, dlen;
+        uint64_t adv;
+        int rc = src.head(pos, x);
+        if (rc) return rc;
+        const int r = snappy_container_step(x, src.clen - pos, format, s.first, &s.R, &coff, &cl, &dlen, &adv);
+        if (r < 0) return r;
+        s.first = 0;
+        if (r == 1) {
+            comp->push_back(pos + coff);
+            comp->push_back(cl);
+            outp->push_back(sum);
+            outp->push_back(dlen);
+            sum += dlen;
+        }
+        pos += adv;
+    }
+    return SNAPPY_AMD_OK;
+}
+
+// out[0, length) = decoded bytes [start, start + length) of the container; with
+// `own` the output is own's, sized only once the walk has shown that the range
+// exists.  An allocation that fails is SNAPPY_AMD_ERR_DEVICE, as in the other host forms.
+int container_range_walked(const ContainerSource &src, FILE *file, int format, uint64_t start, uint64_t length,
+                           uint8_t *out, std::vector<uint8_t> *own)
+{
+    if (start + length < start) return SNAPPY_AMD_ERR_ARG;
+    std::vector<uint64_t> comp, outp;
+    int rc = container_walk_to(src, format, start + length, &comp, &outp);
+    if (rc) return rc;
+    const uint64_t nchunks = outp.size() / 2;
+    const snappy_amd_range whole = {start, length, 0};
+    uint64_t u0, u1, k;
+    // (a walk from the stream's first byte: outp[0] = 0, so ERR_ARG is a range past the decoded bytes)
+    if ((rc = snappy_container_span(outp.data(), nchunks, whole, length, &u0, &u1, &k))) return rc;
+    if (k == 0) return SNAPPY_AMD_OK;
+    if (own) {
+        own->resize((size_t)length);
+        out = own->data();
+    }
+    const uint64_t w0 = comp[2 * u0], w1 = comp[2 * u1] + comp[2 * u1 + 1];
+    std::vector<uint8_t> win((size_t)(w1 - w0));
+    if (src.mem) {
+        memcpy(win.data(), src.mem + w0, win.size());
+    } else {
+        if (fseeko(file, src.base + (off_t)w0, SEEK_SET) != 0) return SNAPPY_AMD_ERR_IO;
+        if (fread(win.data(), 1, win.size(), file) != win.size()) return SNAPPY_AMD_ERR_IO;
+    }
+    HostLease h;
+    if (h.rc()) return h.rc();
+    snappy_amd_ctx *c = h.ctx();
+    // the window at the address residue its first byte has in the stream; the sub-tables
+    // of chunks u0 .. u1, offsets absolute; the output as aligned as the range.  (The tables
+    // go to k5copy: f_meta, k5buf and d_idx are the range call's and the decoder's own.)
+    const size_t pad = (size_t)(w0 & 3), oo = (size_t)(start & 15), pairs = 2 * (size_t)k;
+    if ((rc = grow(reinterpret_cast<void **>(&c->d_a), &c->d_a_cap, win.size() + pad + 16))) return rc;
+    if ((rc = grow(reinterpret_cast<void **>(&c->d_b), &c->d_b_cap, (size_t)length + oo + 16))) return rc;
+    if ((rc = grow(reinterpret_cast<void **>(&c->k5copy), &c->k5copy_cap, 2 * pairs * sizeof(uint64_t)))) return rc;
+    uint64_t *d_tab = reinterpret_cast<uint64_t *>(c->k5copy);
+    HIP_OK(hipMemcpyAsync(c->d_a + pad, win.data(), win.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_tab, comp.data() + 2 * u0, pairs * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_tab + pairs, outp.data() + 2 * u0, pairs * sizeof(uint64_t), hipMemcpyHostToDevice,
+                          c->stream));
+    const snappy_amd_range r = {start, length, oo};
+    if ((rc = snappy_amd_decompress_container_ranges_device(c, c->d_a + pad, w0, win.size(), d_tab, d_tab + pairs,
+                                                            (size_t)k, &r, 1, c->d_b, (size_t)length + oo, nullptr)))
+        return rc;
+    HIP_OK(hipMemcpyAsync(out, c->d_b + oo, (size_t)length, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return SNAPPY_AMD_OK;
+}
+
+int container_range_core(const ContainerSource &src, FILE *file, int format, uint64_t start, uint64_t length,
+                         uint8_t *out, std::vector<uint8_t> *own = nullptr)
+{
+    try {
+        return container_range_walked(src, file, format, start, length, out, own);
+    } catch (const std::bad_alloc &) {
+        return SNAPPY_AMD_ERR_DEVICE;
+    } catch (const std::length_error &) {
+        return SNAPPY_AMD_ERR_DEVICE;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -310,6 +443,56 @@ int snappy_decompress_file_container(FILE *fin, int format, FILE *fout)
         have -= stop;
     }
     return fflush(fout) ? SNAPPY_AMD_ERR_IO : SNAPPY_AMD_OK;
+}
+
+int snappy_container_tables(const uint8_t *in, size_t n, int format, uint64_t *comp_off_len, uint64_t *out_off_len,
+                            size_t max_chunks, size_t *nchunks_out, uint64_t *len)
+{
+    if ((!in && n) || !known(format)) return SNAPPY_AMD_ERR_ARG;
+    std::vector<uint64_t> comp, outp;
+    uint64_t total = 0;
+    WalkState s = {format == SNAPPY_AMD_CONTAINER_XERIAL, 0};
+    const int rc = container_walk_host(in, n, format, &s, true, &comp, &outp, &total, nullptr);
+    if (rc) return rc;
+    if (nchunks_out) *nchunks_out = comp.size() / 2;
+    if (len) *len = total;
+    if ((comp_off_len || out_off_len) && comp.size() / 2 > max_chunks) return SNAPPY_AMD_ERR_CAPACITY;
+    if (comp_off_len && !comp.empty()) memcpy(comp_off_len, comp.data(), comp.size() * sizeof(uint64_t));
+    if (out_off_len && !outp.empty()) memcpy(out_off_len, outp.data(), outp.size() * sizeof(uint64_t));
+    return SNAPPY_AMD_OK;
+}
+
+int snappy_decompress_container_range_buffer(const uint8_t *in, size_t n, int format, uint64_t start, size_t length,
+                                             uint8_t *out, size_t cap, size_t *out_len)
+{
+    if (!out_len || (n && !in) || (length && !out) || !known(format)) return SNAPPY_AMD_ERR_ARG;
+    *out_len = 0;
+    if (length > cap) return SNAPPY_AMD_ERR_CAPACITY;
+    ContainerSource src;
+    src.clen = n;
+    src.mem = in;
+    const int rc = container_range_core(src, nullptr, format, start, length, out);
+    if (rc == SNAPPY_AMD_OK) *out_len = length;
+    return rc;
+}
+
+int snappy_decompress_file_container_range(FILE *file_input, int format, uint64_t start, uint64_t length,
+                                           FILE *file_out)
+{
+    if (!file_input || !file_out || !known(format)) return SNAPPY_AMD_ERR_ARG;
+    ContainerSource src;
+    src.fd = fileno(file_input);
+    src.base = ftello(file_input);
+    if (src.fd < 0 || src.base < 0 || fseeko(file_input, 0, SEEK_END) != 0) return SNAPPY_AMD_ERR_UNSUPPORTED;
+    const off_t end = ftello(file_input);
+    if (end < src.base) return SNAPPY_AMD_ERR_UNSUPPORTED;
+    src.clen = (uint64_t)(end - src.base);
+    // (the output is allocated by the core, after the walk has found the range inside the stream)
+    std::vector<uint8_t> out;
+    const int rc = container_range_core(src, file_input, format, start, length, nullptr, &out);
+    if (rc) return rc;
+    if (length && fwrite(out.data(), 1, (size_t)length, file_out) != length) return SNAPPY_AMD_ERR_IO;
+    return fflush(file_out) ? SNAPPY_AMD_ERR_IO : SNAPPY_AMD_OK;
 }
 
 }  // extern "C"

@@ -190,6 +190,16 @@ __attribute__((visibility("hidden"))) void ranges_launch_status(hipStream_t stre
 __attribute__((visibility("hidden"))) void frame_launch_crc32c(hipStream_t stream, const void *d_base,
                                                                const uint64_t *d_off_len, uint64_t count, int masked,
                                                                uint32_t *d_crc);
+// snappy_long_records.hip, for the container range decode (snappy_container_ranges.hip):
+// the launches of decompress_long_records_device on c->stream after its argument
+// checks.  check_out = false: no record is refused for its output range (the offsets
+// count from d_out, which may be null: then they are addresses).
+__attribute__((visibility("hidden"))) int long_records_launch_decode(snappy_amd_ctx *c, const void *d_comp,
+                                                                     size_t comp_bytes, const uint64_t *d_comp_off_len,
+                                                                     size_t count, void *d_out, size_t out_bytes,
+                                                                     const uint64_t *d_out_off_len,
+                                                                     const uint64_t *d_index, int32_t *d_status,
+                                                                     bool check_out, int sync);
 
 // ---- range decode of a framed stream (snappy_frame_ranges.hip): the planned units
 // of snappy_frame_ranges.h, each one data chunk of the stream

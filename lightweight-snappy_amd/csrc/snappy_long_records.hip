@@ -477,9 +477,26 @@ int snappy_amd_decompress_long_records_device(snappy_amd_ctx *c, const void *d_c
     if (count == 0) return SNAPPY_AMD_OK;
     int rc = call_begin(c);
     if (rc) return rc;
+    return long_records_launch_decode(c, d_comp, comp_bytes, d_comp_off_len, count, d_out, out_bytes, d_out_off_len,
+                                      d_index, d_status, true, sync);
+}
+
+}  // extern "C"
+
+// ---- shared with the container range decode (snappy_container_ranges.hip; declared in
+// snappy_kernels.h): the decode of a checked batch on c->stream.  check_out = false: the
+// output offsets are the caller's own (they count from d_out, which may be null: then
+// they are addresses) and no record is refused for leaving [0, out_bytes).
+int snappy_amd::long_records_launch_decode(snappy_amd_ctx *c, const void *d_comp, size_t comp_bytes,
+                                           const uint64_t *d_comp_off_len, size_t count, void *d_out, size_t out_bytes,
+                                           const uint64_t *d_out_off_len, const uint64_t *d_index, int32_t *d_status,
+                                           bool check_out, int sync)
+{
+    int rc;
     RecTables t;
     LongPlan p;
-    if ((rc = plan_decode(c, comp_bytes, d_comp_off_len, count, out_bytes, d_out_off_len, true, &t, &p))) return rc;
+    if ((rc = plan_decode(c, comp_bytes, d_comp_off_len, count, out_bytes, d_out_off_len, check_out, &t, &p)))
+        return rc;
     if (p.units > 0x7FFFFFFFull) return SNAPPY_AMD_ERR_ARG;
     const size_t units = (size_t)p.units;
     // per unit the unit -> record word and a status word, per record pass 2's two words
@@ -528,5 +545,3 @@ int snappy_amd_decompress_long_records_device(snappy_amd_ctx *c, const void *d_c
     HIP_OK(hipStreamSynchronize(c->stream));
     return first_status(*c->h_total);
 }
-
-}  // extern "C"

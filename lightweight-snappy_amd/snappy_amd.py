@@ -216,6 +216,17 @@ _SIGS = {
                                                         _c.POINTER(_c.c_uint64)]),
     "snappy_compress_file_container": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_uint32, _c.c_int, _c.c_void_p]),
     "snappy_decompress_file_container": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p]),
+    # range decode of containers
+    "snappy_amd_decompress_container_ranges_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_size_t,
+                                                                 _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                                 _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "snappy_container_tables": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                           _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_uint64)]),
+    "snappy_decompress_container_range_buffer": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_uint64,
+                                                            _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                                            _c.POINTER(_c.c_size_t)]),
+    "snappy_decompress_file_container_range": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_uint64, _c.c_uint64,
+                                                          _c.c_void_p]),
 }
 # the reference Buffer cursor helpers, in libsnappy_amd_compat.so (Buffer* is a
 # struct of two pointers and a u32)
@@ -483,6 +494,35 @@ def decompress_container(data, format, cap: Optional[int] = None) -> bytes:
     out = ctypes.create_string_buffer(max(cap, 1))
     got = ctypes.c_size_t(0)
     _check(lib().snappy_decompress_container_buffer(p, n, fmt, out, cap, ctypes.byref(got)), "decompress_container")
+    return out.raw[: got.value]
+
+
+def container_tables(data, format):
+    """(payload pairs, output pairs, decoded bytes) of a container stream: the
+    header walk on the host, no kernel.  Both tables are flat lists of (offset,
+    length) pairs, one pair per chunk, as container_index_tensor gives them."""
+    fmt = container_format(format)
+    p, n, keep = _buf(data)
+    room = n // 5 + 1  # (a container holds at most one chunk per 5 bytes)
+    comp, outp = (ctypes.c_uint64 * (2 * room))(), (ctypes.c_uint64 * (2 * room))()
+    nch, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    _check(lib().snappy_container_tables(p, n, fmt, comp, outp, room, ctypes.byref(nch), ctypes.byref(total)),
+           "container_tables")
+    return list(comp[: 2 * nch.value]), list(outp[: 2 * nch.value]), total.value
+
+
+def decompress_container_range(data, format, start: int, length: int) -> bytes:
+    """Bytes [start, start + length) of decompress_container(data, format): the
+    headers are walked on the host up to the range's last chunk and only the
+    chunks the range touches are uploaded."""
+    fmt = container_format(format)
+    p, n, keep = _buf(data)
+    if start < 0 or length < 0:
+        raise SnappyError(ERR_ARG, "decompress_container_range")
+    out = ctypes.create_string_buffer(max(length, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().snappy_decompress_container_range_buffer(p, n, fmt, start, length, out, length, ctypes.byref(got)),
+           "decompress_container_range")
     return out.raw[: got.value]
 
 
@@ -936,6 +976,38 @@ class Codec:
             ctypes.c_void_p(outp.data_ptr() if outp is not None else 0), nch, ctypes.c_void_p(out.data_ptr()), cap,
             ctypes.byref(got)), "decompress_container_device")
         return out[: got.value]
+
+    def decompress_container_ranges_tensor(self, window, comp_origin: int, comp, outp, ranges, out=None):
+        """Decode the byte ranges `ranges` -- a list or array of (start, length,
+        out_offset) -- of the container whose bytes [comp_origin, comp_origin +
+        window.numel()) are `window`, through its chunk tables (or any contiguous
+        run of their pairs; int64 CUDA tensors, offsets absolute).  Range i lands at
+        out[out_offset_i : out_offset_i + length_i]; out=None allocates
+        max(out_offset + length) bytes.  Returns (out, status): an int32 CUDA tensor
+        of each range's status (self.last_ranges_status = the first failure)."""
+        import numpy as np
+        assert window.is_cuda and window.dtype == torch.uint8 and window.is_contiguous()
+        for t in (comp, outp):
+            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+        assert comp.numel() == outp.numel() and comp.numel() % 2 == 0
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 3))
+        count = r.shape[0]
+        if out is None:
+            need = int((r[:, 1] + r[:, 2]).max()) if count else 0
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=window.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        status = torch.zeros(max(count, 1), dtype=torch.int32, device=window.device)
+        nch = comp.numel() // 2
+        self._bind_stream()
+        rc = lib().snappy_amd_decompress_container_ranges_device(
+            self._h, ctypes.c_void_p(window.data_ptr()), comp_origin, window.numel(),
+            ctypes.c_void_p(comp.data_ptr() if nch else 0), ctypes.c_void_p(outp.data_ptr() if nch else 0), nch,
+            r.ctypes.data_as(ctypes.c_void_p), count, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(status.data_ptr()))
+        self.last_ranges_status = rc
+        if rc == ERR_DEVICE or (rc == ERR_ARG and not count):
+            raise SnappyError(rc, "decompress_container_ranges_device")
+        return out, status[:count]
 
     # record batches ------------------------------------------------------------
     def compress_records_tensor(self, base, off_len, out=None, want_status: bool = True, check: bool = False):
