@@ -16,6 +16,7 @@ import container_cases as cc
 import container_model as cm
 import container_ranges_cases as rc
 import container_ranges_model as crm
+import high_positions as hp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "container_ranges_plan_check.c")
@@ -106,6 +107,10 @@ def build_cases():
     for name in list(rc.SLICE)[:4]:
         fmt, stream, raw, comp, outp, ranges, out_bytes = rc.slice_case(name)
         cases.append((out_bytes, 4096, outp, ranges, []))
+    # the shifted chunk tables and ranges of test_high_positions' container cases (one with an entry's
+    # length raised by 1): offsets around 2^32, and the same moved to 2^40 - 2^16 and 2^62 (no GPU test
+    # goes above 2^33); a staging budget of three blocks, as with SNAPPY_AMD_RANGE_SLOTS=3
+    cases += [(out_bytes, 3 * 65536, outp, ranges, []) for out_bytes, outp, ranges in hp.container_plan_cases()]
     cases.append((0, BUDGET, [(0, 10)], [], table_checks()))
     return cases
 

@@ -14,6 +14,7 @@ import subprocess
 import frame_model as fm
 import frame_ranges_cases as fc
 import frame_ranges_model as frm
+import high_positions as hp
 from test_frame import FOREIGN, comp, pieces
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,6 +110,9 @@ def build_cases():
     for name in fc.SLICE_STREAMS:
         chunks, starts, ranges, out_bytes = fc.slice_case(FOREIGN[name]()[0])
         cases.append((out_bytes, starts, ranges, []))
+    # the shifted seek tables and ranges of test_high_positions' framed cases: starts around 2^32, and the
+    # same moved to 2^40 - 2^16 and 2^62 (no GPU test goes above 2^33)
+    cases += [(out_bytes, starts, ranges, []) for out_bytes, starts, ranges in hp.frame_plan_cases()]
     cases.append((0, [0, 10], [], header_checks()))
     return cases
 

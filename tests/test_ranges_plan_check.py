@@ -9,6 +9,7 @@ import shutil
 import struct
 import subprocess
 
+import high_positions as hp
 import ranges_model as rm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,6 +53,9 @@ def build_cases():
     cases.append((100, 100, 0, [(0, 1, 0)]))        # no unit size
     cases.append((100, 100, B + 1, [(0, 1, 0)]))    # a unit above a block
     cases.append((3 * B, 0, B, []))                 # no ranges
+    # the (n, unit) and ranges of test_high_positions' raw cases: units around 2^32 of a stream of more
+    # than 4 GiB, and the same moved to 2^40 - 2^16 and 2^62 (no GPU test goes above 2^33)
+    cases += hp.raw_plan_cases()
     return cases
 
 
