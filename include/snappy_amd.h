@@ -142,7 +142,31 @@ typedef struct snappy_amd_ctx snappy_amd_ctx;
 int snappy_amd_create(int device, snappy_amd_ctx **ctx);
 void snappy_amd_destroy(snappy_amd_ctx *ctx);
 /* Launch on this hipStream_t (NULL = the context's own stream, a blocking
- * stream: ordered after work queued on the legacy default stream). */
+ * stream: ordered after work queued on the legacy default stream).
+ *
+ * The calls of one context are ordered by its bound stream and by nothing
+ * else: every kernel, memset, copy and read-back of a device call goes to the
+ * stream bound when the call is made, so a call reads its inputs after the
+ * work queued on that stream before it, and work queued there afterwards sees
+ * its outputs.  The context's scratch, its result words and the pinned words
+ * it reads back through are shared by all its calls and are safe only in that
+ * order: one context is used from one thread at a time, on one stream at a
+ * time.  A stream may be non-blocking.
+ *
+ * set_stream itself queues and waits for nothing.  Rebinding a context while
+ * work of a queued form (compress_device without out_len, decompress_device_async,
+ * sync = 0, crc32c_device, records_length_device) is still in flight on the
+ * old stream is for the caller to order: the next call would reuse the scratch
+ * on the new stream, and decompress_status reads the status words on the stream
+ * bound when it is called, not on the one the decode was launched on.
+ *
+ * A queued form returns without waiting for the stream, with two exceptions:
+ * a call that needs a scratch buffer larger than the context holds frees the
+ * old one first, and hipFree waits for the device (so the work still using it
+ * has ended: growing is safe, but not asynchronous); and decompress_ranges_device
+ * waits for the previous range call's plan upload -- not for its kernels --
+ * before it rewrites the pinned plan.  trim and destroy synchronise the bound
+ * stream before they free anything. */
 int snappy_amd_set_stream(snappy_amd_ctx *ctx, void *hip_stream);
 void *snappy_amd_get_stream(snappy_amd_ctx *ctx);
 
