@@ -498,9 +498,14 @@ int snappy_decompress_file_range(FILE *file_input, FILE *idx, uint64_t start, ui
  * length, and for data chunks the masked CRC-32C of the chunk's uncompressed
  * bytes in front of the payload.  A data chunk holds at most 65,536
  * uncompressed bytes, as its own raw Snappy stream (type 00) or stored (type
- * 01).  The compressor here always writes type 00 chunks of 65,536 input
- * bytes (the last one shorter), each payload equal to the SNAPPY_AMD_STREAMS
- * unit of that piece, so the output is a pure function of the input.  The
+ * 01).  The compressor here cuts the input into chunks of `chunk` bytes
+ * (1..65,536; 65,536 for the calls without that argument; the last one may be
+ * shorter).  A compressed chunk's payload equals the SNAPPY_AMD_STREAMS unit of
+ * that piece.  With SNAPPY_AMD_FRAME_STORE a chunk of R input bytes whose unit
+ * has P bytes (preamble included) is written stored (type 01, 24-bit R + 4, the
+ * CRC, the R bytes) iff P >= R - R / 8 (integer division): the payload is not
+ * one eighth smaller than the bytes.  Without the flag every chunk is type 00.
+ * The output is a pure function of (input, chunk, flags).  The
  * decoder takes what other writers emit: stored chunks, padding (fe) and
  * skippable (80..fd) chunks, repeated identifiers, data chunks of any
  * lengths.  Copies cannot reach outside their chunk (ERR_OFFSET).
@@ -526,6 +531,7 @@ int snappy_decompress_file_range(FILE *file_input, FILE *idx, uint64_t start, ui
  *   ERR_INDEX        a chunk table entry that is not a data chunk's header
  *   ERR_CHECKSUM     CRC mismatch;  element errors as the decoder reports them */
 #define SNAPPY_AMD_FRAME_NO_IDENTIFIER 1u /* this buffer continues a framed stream */
+#define SNAPPY_AMD_FRAME_STORE 2u   /* a chunk whose payload is not 1/8 smaller than its bytes is stored (type 01) */
 
 /* CRC-32C (polynomial 0x82F63B78 reflected, init and xor-out ffffffff) of
  * `count` byte ranges of d_base: d_off_len holds (offset, length) pairs, any
@@ -541,6 +547,18 @@ size_t snappy_amd_max_frame_output(size_t n);
  * entries.  n == 0 writes the identifier alone. */
 int snappy_amd_compress_frame_device(snappy_amd_ctx *ctx, const void *d_in, size_t n, uint32_t flags, void *d_out,
                                      uint64_t *d_chunks, size_t *out_len);
+/* The same with the chunk size and the store rule (above): chunk = input bytes
+ * per data chunk, 1..65,536 (else ERR_ARG, and max_frame_output_ex returns 0);
+ * flags = SNAPPY_AMD_FRAME_NO_IDENTIFIER | SNAPPY_AMD_FRAME_STORE (any other bit:
+ * ERR_ARG).  compress_frame_device is chunk 65,536 and accepts NO_IDENTIFIER only.
+ * Capacity: 10 + 8 ceil(n / chunk) + snappy_amd_max_output(n, chunk,
+ * SNAPPY_AMD_STREAMS), whatever the flags (a stored chunk, 8 + R bytes, is never
+ * larger than a compressed one's bound).  d_chunks receives ceil(n / chunk) + 1
+ * entries; more than 2^31 - 1 chunks is ERR_ARG.  The flag adds no read-back:
+ * with out_len == NULL the call is queued on the context stream and returns. */
+size_t snappy_amd_max_frame_output_ex(size_t n, uint32_t chunk);
+int snappy_amd_compress_frame_device_ex(snappy_amd_ctx *ctx, const void *d_in, size_t n, uint32_t chunk,
+                                        uint32_t flags, void *d_out, uint64_t *d_chunks, size_t *out_len);
 /* Walk a framed stream in HBM from its identifier: d_chunks (room for
  * max_chunks entries, the closing one included) gets the chunk table,
  * *nchunks_out the data chunks, *n_out the decoded bytes.  One wave follows
@@ -562,6 +580,13 @@ int snappy_amd_decompress_frame_device(snappy_amd_ctx *ctx, const void *d_frame,
  * sets another piece size for the buffer and FILE* compressors and the FILE*
  * decoder's read buffer; the bytes written do not depend on it). */
 int snappy_compress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len);
+/* With a chunk size and flags (SNAPPY_AMD_FRAME_STORE only: the host forms place
+ * the identifier themselves): out must hold snappy_amd_max_frame_output_ex(n,
+ * chunk).  A piece is the piece size rounded down to a multiple of chunk (at
+ * least one chunk), so the bytes written do not depend on it.  The forms without
+ * these arguments are (65536, 0). */
+int snappy_compress_frame_buffer_ex(const uint8_t *in, size_t n, uint32_t chunk, uint32_t flags, uint8_t *out,
+                                    size_t cap, size_t *out_len);
 int snappy_decompress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len);
 /* Decoded bytes of a framed stream: the chunk walk on the host (no kernel),
  * the same rules as frame_index_device. */
@@ -569,6 +594,8 @@ int snappy_frame_uncompressed_length(const uint8_t *in, size_t n, uint64_t *len)
 /* FILE* forms: file_input from its current position to EOF (input_size is
  * not needed: the format stores no total length). */
 int snappy_compress_file_framed(FILE *file_input, unsigned long long input_size, FILE *file_compressed);
+int snappy_compress_file_framed_ex(FILE *file_input, unsigned long long input_size, uint32_t chunk, uint32_t flags,
+                                   FILE *file_compressed);
 int snappy_decompress_file_framed(FILE *file_input, FILE *file_decompressed);
 
 /* ---- range decode of a framed stream: seek table, CRC-checked slices ------ */
@@ -583,7 +610,8 @@ int snappy_decompress_file_framed(FILE *file_input, FILE *file_decompressed);
  * frame_seek_device builds it from a chunk table: every entry's header is
  * checked as decompress_frame_device checks it (the same codes, the first
  * failing entry's), then the lengths are scanned.  *n_out = the decoded length.
- * compress_frame_device's own streams give starts[i] = min(65536 i, n).
+ * compress_frame_device's own streams give starts[i] = min(65536 i, n)
+ * (compress_frame_device_ex's: min(chunk i, n)).
  * snappy_frame_tables is the same on host memory, with no kernel: the chunk
  * walk of frame_index_device and both tables (room for max_chunks entries each,
  * the closing ones included; either may be NULL). */

@@ -9,6 +9,10 @@
  * -f (an addition): with -c write, with -d read the Snappy framing format
  * (framing_format.txt of google/snappy), the file format of other Snappy
  * tools; not with -b or -i.
+ * -k bytes, -s (additions): with -c -f only.  -k gives the input bytes per data
+ * chunk (1..65536; 65536 without it), the price of a small -R read; -s writes a
+ * chunk whose compressed payload is not one eighth smaller than its bytes as a
+ * stored chunk (type 01).
  * -F hadoop|xerial (an addition): with -c write, with -d read the container of
  * Hadoop's SnappyCodec (.snappy files) or of snappy-java's SnappyOutputStream;
  * not with -b, -i or -f.
@@ -32,13 +36,15 @@
 static void usage(void)
 {
     fprintf(stderr,
-            "snappy [-c|-d|-b] [-r] [-i] [-f] [-F format] [-R start:length] [infile] [outfile]\n"
+            "snappy [-c|-d|-b] [-r] [-i] [-f] [-k bytes] [-s] [-F format] [-R start:length] [infile] [outfile]\n"
             "-c compress (MI355X)\n"
             "-b compress with the BST matcher\n"
             "-d decompress (MI355X)\n"
             "-r print results\n"
             "-i -c: also write outfile.idx (block index); -d: use infile.idx\n"
             "-f with -c or -d: the Snappy framing format (chunks with CRC-32C)\n"
+            "-k bytes with -c -f: input bytes per chunk, 1..65536 (default 65536)\n"
+            "-s with -c -f: store chunks that do not compress by one eighth (type 01)\n"
             "-F hadoop|xerial with -c or -d: the Hadoop SnappyCodec / snappy-java container\n"
             "-R start:length with -d: only the decoded bytes [start, start + length) (-i: read only their blocks;\n"
             "   -f: of a framed stream, reading only their chunks)\n");
@@ -68,14 +74,25 @@ int main(int argc, char *argv[])
     enum { M_COMPRESS, M_BST, M_DECOMPRESS } mode = M_COMPRESS;
     int show = 0, indexed = 0, framed = 0, container = -1, ranged = 0, compress_flag = 0, opt;
     unsigned long long r_start = 0, r_length = 0;
+    int chunk_given = 0, store = 0;
+    unsigned long chunk = SNAPPY_AMD_BLOCK;
     if (argc < 4) usage();
-    while ((opt = getopt(argc, argv, "cbdrifF:R:")) != -1) {
+    while ((opt = getopt(argc, argv, "cbdrifk:sF:R:")) != -1) {
         if (opt == 'c') mode = M_COMPRESS, compress_flag = 1;
         else if (opt == 'b') mode = M_BST;
         else if (opt == 'd') mode = M_DECOMPRESS;
         else if (opt == 'r') show = 1;
         else if (opt == 'i') indexed = 1;
         else if (opt == 'f') framed = 1;
+        else if (opt == 's') store = 1;
+        else if (opt == 'k') {
+            char *end = NULL;
+            errno = 0;
+            if (optarg[0] < '0' || optarg[0] > '9') usage();
+            chunk = strtoul(optarg, &end, 10);
+            if (errno || *end || chunk == 0 || chunk > SNAPPY_AMD_BLOCK) usage();
+            chunk_given = 1;
+        }
         else if (opt == 'F' && strcmp(optarg, "hadoop") == 0) container = SNAPPY_AMD_CONTAINER_HADOOP;
         else if (opt == 'F' && strcmp(optarg, "xerial") == 0) container = SNAPPY_AMD_CONTAINER_XERIAL;
         else if (opt == 'R') {
@@ -94,6 +111,7 @@ int main(int argc, char *argv[])
     if (indexed && mode == M_BST) usage();  /* -b writes no block index */
     if (framed && (indexed || mode == M_BST)) usage();  /* a framed stream has its chunk headers; -b is unframed */
     if (container >= 0 && (framed || indexed || mode == M_BST)) usage();  /* one file format at a time */
+    if ((chunk_given || store) && !(framed && compress_flag && mode == M_COMPRESS)) usage();  /* -k, -s: the framed writer's */
     if (ranged && (mode != M_DECOMPRESS || compress_flag || container >= 0)) usage();  /* -R: a raw or framed stream's decode */
     const char *in_name = argv[argc - 2], *out_name = argv[argc - 1];
     FILE *in = open_or_die(in_name, "rb");
@@ -116,7 +134,9 @@ int main(int argc, char *argv[])
         rc = snappy_decompress_file_frame_range(in, r_start, r_length, out);
         if (rc != 0) fprintf(stderr, "snappy_decompress_file_frame_range: error %d\n", rc);
     } else if (framed) {
-        rc = mode == M_COMPRESS ? snappy_compress_file_framed(in, in_size, out) : snappy_decompress_file_framed(in, out);
+        rc = mode == M_COMPRESS ? snappy_compress_file_framed_ex(in, in_size, (uint32_t)chunk,
+                                                                 store ? SNAPPY_AMD_FRAME_STORE : 0u, out)
+                                : snappy_decompress_file_framed(in, out);
     } else if (mode == M_COMPRESS && idx) {
         rc = snappy_compress_file_indexed(in, in_size, out, idx);
     } else if (mode == M_COMPRESS) {

@@ -74,12 +74,16 @@ extern "C" SNAPPY_PRIVATE int host_ctx_lease(void **token, snappy_amd_ctx **ctx)
 extern "C" SNAPPY_PRIVATE void host_ctx_return(void *token);
 // The compress launches of every device compress call, on c->stream, for n > 0
 // bytes in units of `unit` (<= SNAPPY_AMD_BLOCK): the scratch sizing, K1r (or
-// K1r64) with the timing events, after_match(c, units) when given (the framed
+// K1r64) with the timing events, after_match(c, units, arg) when given (the framed
 // call adds its chunk headers to c->sizes there), K3 into d_offsets (units + 1
 // entries, the total in c->total) and K2 to d_out.  hdr_mode: SNAPPY_HDR_*.
+// d_skip (when given: one word per unit, written by after_match's launches) makes
+// K2 leave the marked units' slots alone (k2_emit_units_sel); without it the launch
+// is k2_emit_units.
 SNAPPY_PRIVATE int compress_launch(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit, uint32_t hdr_mode,
                                    uint64_t header_value, uint64_t *d_offsets, void *d_out,
-                                   void (*after_match)(snappy_amd_ctx *c, size_t units));
+                                   void (*after_match)(snappy_amd_ctx *c, size_t units, void *arg),
+                                   void *arg = nullptr, const uint32_t *d_skip = nullptr);
 // the argument checks, the n == 0 case and compress_launch for a layout; *out_len
 // (when non-null) after a sync of c->stream, otherwise the size stays in c->total (device)
 extern "C" SNAPPY_PRIVATE int compress_impl(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk, int layout,

@@ -47,7 +47,8 @@ int ctx_stream(snappy_amd_ctx *c)
 
 // register-resident match finder -> tokens; scan; emit in place
 int compress_launch(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit, uint32_t hm, uint64_t header_value,
-                    uint64_t *d_offsets, void *d_out, void (*after_match)(snappy_amd_ctx *c, size_t units))
+                    uint64_t *d_offsets, void *d_out, void (*after_match)(snappy_amd_ctx *c, size_t units, void *arg),
+                    void *arg, const uint32_t *d_skip)
 {
     const size_t units = (n + unit - 1) / unit;
     int rc;
@@ -79,17 +80,23 @@ int compress_launch(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit
                            static_cast<uint2 *>(c->tokens), tok_cap, c->ntok, c->sizes, c->seg_off, segs);
     HIP_OK(hipGetLastError());
     if (c->timing) (void)hipEventRecord(c->ev[1], c->stream);
-    if (after_match) after_match(c, units);
+    if (after_match) after_match(c, units, arg);
     if (units <= SNAPPY_K3_WAVE_MAX)
         hipLaunchKernelGGL(k3_scan_wave, dim3(1), dim3(64), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
     else
         hipLaunchKernelGGL(k3_scan, dim3(1), dim3(1024), 0, c->stream, c->sizes, (uint64_t)units, d_offsets, c->total);
     // K1r wrote the sizes and segment offsets; K2: a few waves per unit, each taking
     // every SNAPPY_K2_WAVES-th segment (text fills ~12 segments of 32 KiB units)
-    hipLaunchKernelGGL(k2_emit_units, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES), dim3(64), 0, c->stream,
-                       static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm, header_value,
-                       static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs, d_offsets,
-                       static_cast<uint8_t *>(d_out));
+    if (!d_skip)
+        hipLaunchKernelGGL(k2_emit_units, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES),
+                           dim3(64), 0, c->stream, static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm,
+                           header_value, static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs,
+                           d_offsets, static_cast<uint8_t *>(d_out));
+    else // (units the caller marked write nothing: the framed call's stored chunks)
+        hipLaunchKernelGGL(k2_emit_units_sel, dim3((uint32_t)units, segs < SNAPPY_K2_WAVES ? segs : SNAPPY_K2_WAVES),
+                           dim3(64), 0, c->stream, static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, hm,
+                           header_value, static_cast<const uint2 *>(c->tokens), tok_cap, c->ntok, c->seg_off, segs,
+                           d_offsets, static_cast<uint8_t *>(d_out), d_skip);
     HIP_OK(hipGetLastError());
     if (c->timing) {
         (void)hipEventRecord(c->ev[2], c->stream);

@@ -59,6 +59,12 @@ SNAPPY_FRAME_FN uint32_t snappy_frame_preamble(const uint8_t *w, uint32_t have, 
     return 0;
 }
 
+// The store rule of the compressor under SNAPPY_AMD_FRAME_STORE (the device's
+// kf2_choose; any host code that has to predict a stream): a chunk of R input
+// bytes whose raw stream (preamble included) has P bytes is written stored
+// (type 01) iff the stream is not one eighth smaller than the bytes.
+SNAPPY_FRAME_FN int snappy_frame_store_chunk(uint32_t R, uint32_t P) { return P >= R - R / 8u; }
+
 // One step of the chunk walk.  w = the first 16 bytes of the chunk at the
 // walk's position (zero past the stream's end), avail = stream bytes from that
 // position on (> 0), first = the stream identifier is still owed.  Returns a

@@ -5,6 +5,8 @@
 //
 //   KF1  kf1_crc32c      batched CRC-32C, one wave per (offset, length) entry
 //   KF2  kf2_headers     identifier + chunk headers around the payloads K2 wrote
+//        kf2_choose      SNAPPY_AMD_FRAME_STORE: which chunks are stored (type 01), their slots
+//        kf2_store       the stored chunks' bytes, 16-byte stores at any alignment pair
 //   KF3  kf3_walk        chunk walk of a foreign stream (one wave, one hop per chunk)
 //   KF4  kf4_scan        per data chunk: header checks, decoded length, scratch bytes
 //        kf4_gather      payloads -> contiguous scratch, as SNAPPY_AMD_STREAMS units
@@ -14,7 +16,8 @@
 // The match finder, the scan, the emitter (K1r64, K3, K2) and the decoder (K4)
 // are the unframed path's kernels, unchanged (the compress ones through the
 // unframed path's own compress_launch, snappy_device.hip): a framed chunk's
-// payload is exactly a STREAMS unit of 65,536 bytes.  Declared in
+// payload is exactly a STREAMS unit of the chunk size (1..65,536 bytes; with
+// FRAME_STORE K2 runs from its entry point k2_emit_units_sel).  Declared in
 // include/snappy_amd.h.  DESIGN.md 7.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -182,12 +185,84 @@ __global__ __launch_bounds__(256) void kf2_bump(uint32_t *__restrict__ sizes, ui
     if (u < units) sizes[u] += 8u;
 }
 
-// offsets/sizes: the scan of the bumped sizes.  Chunk u: 00, 24-bit (4 + payload
-// bytes), masked CRC, at out + ident + offsets[u]; chunks[u] = that position.
+// SNAPPY_AMD_FRAME_STORE: kf2_choose in kf2_bump's place.  One thread per chunk:
+// the store rule (snappy_frame_store_chunk) on the chunk's R input bytes and its
+// stream's P bytes; a stored chunk's slot is its header and its R bytes, so the
+// scan lays the stored chunks out too, and K2 (k2_emit_units_sel) skips them.
+__global__ __launch_bounds__(256) void kf2_choose(uint32_t *__restrict__ sizes, uint64_t units, uint64_t n,
+                                                  uint32_t chunk, uint32_t *__restrict__ stored)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= units) return;
+    const uint64_t at = u * chunk;
+    const uint32_t R = (uint32_t)(n - at < chunk ? n - at : chunk), P = sizes[u];
+    const uint32_t st = snappy_frame_store_chunk(R, P) ? 1u : 0u;
+    stored[u] = st;
+    sizes[u] = (st ? R : P) + 8u;
+}
+
+constexpr uint32_t kF2StoreThreads = 256;  // 4 waves: 4 KiB of a chunk per round of 16-byte stores
+constexpr uint32_t kF2StoreSpan = 16 * kF2StoreThreads;
+constexpr uint32_t kF2StoreParts = 4;      // workgroups per chunk above 3 rounds: 16 waves on 65,536 bytes
+typedef uint32_t kf2_u32x4 __attribute__((ext_vector_type(4)));
+
+// Stored chunk u (blockIdx.x; blockIdx.y = its part): in[u * chunk, + R) to out +
+// ident + offsets[u] + 8.  16-byte stores at the destination's alignment; the source
+// bytes of each come from the four or five aligned dwords that hold them (every
+// dword read holds a byte of the chunk), shifted into place.  Part 0 also writes the
+// < 16 bytes in front of the first aligned store and behind the last.  No byte
+// outside the chunk's R payload bytes is written, none outside in[0, n) read
+// beyond the aligned dwords of its first and last byte.
+__global__ __launch_bounds__(kF2StoreThreads) void kf2_store(const uint8_t *__restrict__ in, uint64_t n, uint32_t chunk,
+                                                             const uint32_t *__restrict__ stored,
+                                                             const uint64_t *__restrict__ offsets, uint32_t ident,
+                                                             uint8_t *__restrict__ out)
+{
+    const uint32_t u = blockIdx.x;
+    if (!stored[u]) return;
+    const uint64_t at = (uint64_t)u * chunk;
+    const uint32_t R = (uint32_t)(n - at < chunk ? n - at : chunk), t = threadIdx.x;
+    const uint8_t *const src = in + at;
+    uint8_t *const dst = out + ident + offsets[u] + 8;
+    const uint32_t h0 = (uint32_t)(-reinterpret_cast<uintptr_t>(dst) & 15);
+    const uint32_t h = h0 < R ? h0 : R;
+    const uint32_t body = (R - h) & ~15u;
+    const uint8_t *const s = src + h;
+    uint8_t *const d = dst + h;
+    const uint32_t sa = (uint32_t)(reinterpret_cast<uintptr_t>(s) & 3);
+    const uint32_t *const s4 = reinterpret_cast<const uint32_t *>(s - sa);
+    const uint32_t first = (blockIdx.y * kF2StoreThreads + t) * 16u, step = gridDim.y * kF2StoreSpan;
+    if (sa == 0) {
+        for (uint32_t x = first; x < body; x += step) {
+            const uint32_t *const q = s4 + x / 4;
+            const kf2_u32x4 v = {q[0], q[1], q[2], q[3]};
+            *reinterpret_cast<kf2_u32x4 *>(d + x) = v;
+        }
+    } else {
+        const uint32_t sh = 8 * sa;
+        for (uint32_t x = first; x < body; x += step) {
+            const uint32_t *const q = s4 + x / 4;
+            const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4];
+            const kf2_u32x4 v = {__builtin_amdgcn_alignbit(w1, w0, sh), __builtin_amdgcn_alignbit(w2, w1, sh),
+                                 __builtin_amdgcn_alignbit(w3, w2, sh), __builtin_amdgcn_alignbit(w4, w3, sh)};
+            *reinterpret_cast<kf2_u32x4 *>(d + x) = v;
+        }
+    }
+    if (blockIdx.y == 0) {  // h < 16 and R - h - body < 16
+        if (t < h) dst[t] = src[t];
+        const uint32_t done = h + body;
+        if (done + t < R) dst[done + t] = src[done + t];
+    }
+}
+
+// offsets/sizes: the scan of the bumped sizes.  Chunk u: its type (00, or 01 where
+// stored[u] is set; stored null: all 00), 24-bit (4 + payload bytes), masked CRC, at
+// out + ident + offsets[u]; chunks[u] = that position.
 __global__ __launch_bounds__(256) void kf2_headers(uint8_t *__restrict__ out, uint32_t ident,
                                                    const uint64_t *__restrict__ offsets,
                                                    const uint32_t *__restrict__ sizes,
-                                                   const uint32_t *__restrict__ crc, uint64_t units,
+                                                   const uint32_t *__restrict__ crc,
+                                                   const uint32_t *__restrict__ stored, uint64_t units,
                                                    uint64_t *__restrict__ chunks)
 {
     const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -200,7 +275,7 @@ __global__ __launch_bounds__(256) void kf2_headers(uint8_t *__restrict__ out, ui
     const uint64_t at = ident + offsets[u];
     const uint32_t len = sizes[u] - 8u + 4u, c = crc[u];
     uint8_t *h = out + at;
-    h[0] = 0x00;
+    h[0] = stored && stored[u] ? 0x01 : 0x00;
     h[1] = (uint8_t)len;
     h[2] = (uint8_t)(len >> 8);
     h[3] = (uint8_t)(len >> 16);
@@ -415,41 +490,73 @@ int snappy_amd_crc32c_device(snappy_amd_ctx *c, const void *d_base, const uint64
     return SNAPPY_AMD_OK;
 }
 
-size_t snappy_amd_max_frame_output(size_t n)
+size_t snappy_amd_max_frame_output_ex(size_t n, uint32_t chunk)
 {
-    const size_t units = (n + SNAPPY_AMD_BLOCK - 1) / SNAPPY_AMD_BLOCK;
-    return SNAPPY_FRAME_IDENT_LEN + 8 * units + snappy_amd_max_output(n, SNAPPY_AMD_BLOCK, SNAPPY_AMD_STREAMS);
+    if (chunk == 0 || chunk > SNAPPY_FRAME_CHUNK_MAX) return 0;
+    const size_t units = (n + chunk - 1) / chunk;
+    return SNAPPY_FRAME_IDENT_LEN + 8 * units + snappy_amd_max_output(n, chunk, SNAPPY_AMD_STREAMS);
 }
 
-int snappy_amd_compress_frame_device(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t flags, void *d_out,
-                                     uint64_t *d_chunks, size_t *out_len)
+size_t snappy_amd_max_frame_output(size_t n) { return snappy_amd_max_frame_output_ex(n, SNAPPY_AMD_BLOCK); }
+
+namespace {
+struct ChooseArgs {
+    size_t n;
+    uint32_t chunk;
+    uint32_t *stored;
+};
+
+// `flags` checked by the caller; chunk in 1..65,536
+int frame_compress_device(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t unit, uint32_t flags, void *d_out,
+                          uint64_t *d_chunks, size_t *out_len)
 {
-    if (!c || (!d_in && n) || !d_out || !d_chunks || (flags & ~SNAPPY_AMD_FRAME_NO_IDENTIFIER)) return SNAPPY_AMD_ERR_ARG;
-    const uint32_t unit = SNAPPY_AMD_BLOCK;
+    if (!c || (!d_in && n) || !d_out || !d_chunks) return SNAPPY_AMD_ERR_ARG;
     const size_t units = (n + unit - 1) / unit;
     if (units > 0x7FFFFFFFull) return SNAPPY_AMD_ERR_ARG;
     int rc = frame_call_begin(c);
     if (rc) return rc;
     const uint32_t ident = (flags & SNAPPY_AMD_FRAME_NO_IDENTIFIER) ? 0u : SNAPPY_FRAME_IDENT_LEN;
+    const bool store = (flags & SNAPPY_AMD_FRAME_STORE) != 0;
     uint8_t *out = static_cast<uint8_t *>(d_out);
     uint64_t *f_off = nullptr;
-    uint32_t *f_crc = nullptr;
+    uint32_t *f_crc = nullptr, *f_stored = nullptr;
     if (units) {
+        // scan offsets | CRCs | (FRAME_STORE) the chunks' stored words
         if ((rc = grow(reinterpret_cast<void **>(&c->f_meta), &c->f_meta_cap,
-                       (units + 1) * sizeof(uint64_t) + units * sizeof(uint32_t))))
+                       (units + 1) * sizeof(uint64_t) + units * sizeof(uint32_t) * (store ? 2 : 1))))
             return rc;
         f_off = reinterpret_cast<uint64_t *>(c->f_meta);
         f_crc = reinterpret_cast<uint32_t *>(f_off + units + 1);
-        // STREAMS units of 65,536, with kf2_bump between K1r64 and the scan (KF2 above)
-        auto bump = [](snappy_amd_ctx *cc, size_t nu) {
-            hipLaunchKernelGGL(kf2_bump, dim3(blocks_of(nu, 256)), dim3(256), 0, cc->stream, cc->sizes, (uint64_t)nu);
-        };
-        if ((rc = compress_launch(c, d_in, n, unit, SNAPPY_HDR_EVERY_UNIT, (uint64_t)n, f_off, out + ident + 8, bump)))
-            return rc;
+        if (!store) {
+            // STREAMS units of `unit` bytes, with kf2_bump between the match finder and the scan (KF2 above)
+            auto bump = [](snappy_amd_ctx *cc, size_t nu, void *) {
+                hipLaunchKernelGGL(kf2_bump, dim3(blocks_of(nu, 256)), dim3(256), 0, cc->stream, cc->sizes, (uint64_t)nu);
+            };
+            if ((rc = compress_launch(c, d_in, n, unit, SNAPPY_HDR_EVERY_UNIT, (uint64_t)n, f_off, out + ident + 8, bump)))
+                return rc;
+        } else {
+            // kf2_choose there instead; K2 leaves the stored chunks' slots to kf2_store
+            f_stored = f_crc + units;
+            ChooseArgs a = {n, unit, f_stored};
+            auto choose = [](snappy_amd_ctx *cc, size_t nu, void *arg) {
+                const ChooseArgs *ca = static_cast<const ChooseArgs *>(arg);
+                hipLaunchKernelGGL(kf2_choose, dim3(blocks_of(nu, 256)), dim3(256), 0, cc->stream, cc->sizes,
+                                   (uint64_t)nu, (uint64_t)ca->n, ca->chunk, ca->stored);
+            };
+            if ((rc = compress_launch(c, d_in, n, unit, SNAPPY_HDR_EVERY_UNIT, (uint64_t)n, f_off, out + ident + 8, choose,
+                                      &a, f_stored)))
+                return rc;
+        }
         launch_kf1(c, d_in, nullptr, units, unit, n, 1, f_crc);
+        if (store) {
+            const uint32_t rounds = (unit + kF2StoreSpan - 1) / kF2StoreSpan;
+            hipLaunchKernelGGL(kf2_store, dim3((uint32_t)units, rounds > 3 ? kF2StoreParts : 1u), dim3(kF2StoreThreads), 0,
+                               c->stream, static_cast<const uint8_t *>(d_in), (uint64_t)n, unit, f_stored, f_off, ident,
+                               out);
+        }
     }
     hipLaunchKernelGGL(kf2_headers, dim3(units ? blocks_of(units, 256) : 1u), dim3(256), 0, c->stream, out, ident,
-                       f_off, c->sizes, f_crc, (uint64_t)units, d_chunks);
+                       f_off, c->sizes, f_crc, f_stored, (uint64_t)units, d_chunks);
     HIP_OK(hipGetLastError());
     if (out_len) {
         *c->h_total = 0;
@@ -458,6 +565,22 @@ int snappy_amd_compress_frame_device(snappy_amd_ctx *c, const void *d_in, size_t
         *out_len = ident + (size_t)*c->h_total;
     }
     return SNAPPY_AMD_OK;
+}
+}  // namespace
+
+int snappy_amd_compress_frame_device(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t flags, void *d_out,
+                                     uint64_t *d_chunks, size_t *out_len)
+{
+    if (flags & ~SNAPPY_AMD_FRAME_NO_IDENTIFIER) return SNAPPY_AMD_ERR_ARG;
+    return frame_compress_device(c, d_in, n, SNAPPY_AMD_BLOCK, flags, d_out, d_chunks, out_len);
+}
+
+int snappy_amd_compress_frame_device_ex(snappy_amd_ctx *c, const void *d_in, size_t n, uint32_t chunk, uint32_t flags,
+                                        void *d_out, uint64_t *d_chunks, size_t *out_len)
+{
+    if (chunk == 0 || chunk > SNAPPY_FRAME_CHUNK_MAX) return SNAPPY_AMD_ERR_ARG;
+    if (flags & ~(SNAPPY_AMD_FRAME_NO_IDENTIFIER | SNAPPY_AMD_FRAME_STORE)) return SNAPPY_AMD_ERR_ARG;
+    return frame_compress_device(c, d_in, n, chunk, flags, d_out, d_chunks, out_len);
 }
 
 int snappy_amd_frame_index_device(snappy_amd_ctx *c, const void *d_frame, size_t clen, uint64_t *d_chunks,

@@ -25,10 +25,10 @@
 #include "snappy_frame_ranges.h"
 
 namespace {
-// Bytes a call handles at a time: a multiple of the 65,536-byte chunk, so the
-// chunks of a piece are those of the whole input.  SNAPPY_AMD_FRAME_PIECE_KB
-// (a multiple of 64, read at every call) sets another size: the tests use it
-// to cross piece boundaries with small inputs.
+// Bytes a call handles at a time.  SNAPPY_AMD_FRAME_PIECE_KB (a multiple of 64,
+// read at every call) sets another size: the tests use it to cross piece
+// boundaries with small inputs.  The compressors cut pieces of compress_piece_bytes:
+// a multiple of the chunk size, so the chunks of a piece are those of the whole input.
 size_t piece_bytes()
 {
     const char *e = getenv("SNAPPY_AMD_FRAME_PIECE_KB");
@@ -36,6 +36,9 @@ size_t piece_bytes()
     if (kb >= 64 && kb % 64 == 0 && kb <= (4l << 20)) return (size_t)kb << 10;
     return (size_t)64 << 20;
 }
+
+// the piece size rounded down to a multiple of `chunk` (1..65,536 <= a piece): at least one chunk
+size_t compress_piece_bytes(uint32_t chunk) { return piece_bytes() / chunk * chunk; }
 
 class HostLease {
 public:
@@ -102,17 +105,17 @@ int frame_walk_host(const uint8_t *in, size_t n, bool need_ident, std::vector<ui
     return rc;
 }
 
-// frame in[0..n) (at most one piece) on context c, *len bytes to out
-int frame_compress_piece(snappy_amd_ctx *c, const uint8_t *in, size_t n, uint32_t flags, uint8_t *out, size_t cap,
-                         size_t *len)
+// frame in[0..n) (at most one piece) in chunks of `chunk` bytes on context c, *len bytes to out
+int frame_compress_piece(snappy_amd_ctx *c, const uint8_t *in, size_t n, uint32_t chunk, uint32_t flags, uint8_t *out,
+                         size_t cap, size_t *len)
 {
-    const size_t units = (n + SNAPPY_AMD_BLOCK - 1) / SNAPPY_AMD_BLOCK;
+    const size_t units = (n + chunk - 1) / chunk;
     int rc;
     if ((rc = grow(reinterpret_cast<void **>(&c->d_a), &c->d_a_cap, n + 16))) return rc;
-    if ((rc = grow(reinterpret_cast<void **>(&c->d_b), &c->d_b_cap, snappy_amd_max_frame_output(n)))) return rc;
+    if ((rc = grow(reinterpret_cast<void **>(&c->d_b), &c->d_b_cap, snappy_amd_max_frame_output_ex(n, chunk)))) return rc;
     if ((rc = grow(reinterpret_cast<void **>(&c->d_idx), &c->d_idx_cap, (units + 1) * sizeof(uint64_t)))) return rc;
     if (n) HIP_OK(hipMemcpyAsync(c->d_a, in, n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = snappy_amd_compress_frame_device(c, c->d_a, n, flags, c->d_b, c->d_idx, len))) return rc;
+    if ((rc = snappy_amd_compress_frame_device_ex(c, c->d_a, n, chunk, flags, c->d_b, c->d_idx, len))) return rc;
     if (*len > cap) return SNAPPY_AMD_ERR_CAPACITY;
     if (*len) HIP_OK(hipMemcpyAsync(out, c->d_b, *len, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -276,18 +279,25 @@ int snappy_frame_uncompressed_length(const uint8_t *in, size_t n, uint64_t *len)
 
 int snappy_compress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len)
 {
+    return snappy_compress_frame_buffer_ex(in, n, SNAPPY_AMD_BLOCK, 0u, out, cap, out_len);
+}
+
+int snappy_compress_frame_buffer_ex(const uint8_t *in, size_t n, uint32_t chunk, uint32_t flags, uint8_t *out,
+                                    size_t cap, size_t *out_len)
+{
     if (!out_len || (!in && n) || !out) return SNAPPY_AMD_ERR_ARG;
     *out_len = 0;
+    if (chunk == 0 || chunk > SNAPPY_FRAME_CHUNK_MAX || (flags & ~SNAPPY_AMD_FRAME_STORE)) return SNAPPY_AMD_ERR_ARG;
     HostLease h;
     if (h.rc()) return h.rc();
     // chunk sequences concatenate: every piece after the first without the identifier
-    const size_t kPiece = piece_bytes();
+    const size_t kPiece = compress_piece_bytes(chunk);
     size_t at = 0, done = 0;
     do {
         const size_t piece = n - done < kPiece ? n - done : kPiece;
         size_t len = 0;
-        int rc = frame_compress_piece(h.ctx(), in + done, piece, done ? SNAPPY_AMD_FRAME_NO_IDENTIFIER : 0u, out + at,
-                                      cap - at, &len);
+        int rc = frame_compress_piece(h.ctx(), in + done, piece, chunk,
+                                      flags | (done ? SNAPPY_AMD_FRAME_NO_IDENTIFIER : 0u), out + at, cap - at, &len);
         if (rc) return rc;
         at += len;
         done += piece;
@@ -314,20 +324,27 @@ int snappy_decompress_frame_buffer(const uint8_t *in, size_t n, uint8_t *out, si
 
 int snappy_compress_file_framed(FILE *fin, unsigned long long input_size, FILE *fout)
 {
+    return snappy_compress_file_framed_ex(fin, input_size, SNAPPY_AMD_BLOCK, 0u, fout);
+}
+
+int snappy_compress_file_framed_ex(FILE *fin, unsigned long long input_size, uint32_t chunk, uint32_t flags, FILE *fout)
+{
     (void)input_size;
     if (!fin || !fout) return SNAPPY_AMD_ERR_ARG;
+    if (chunk == 0 || chunk > SNAPPY_FRAME_CHUNK_MAX || (flags & ~SNAPPY_AMD_FRAME_STORE)) return SNAPPY_AMD_ERR_ARG;
     HostLease h;
     if (h.rc()) return h.rc();
-    const size_t kPiece = piece_bytes();
-    std::vector<uint8_t> in(kPiece), out(snappy_amd_max_frame_output(kPiece));
+    const size_t kPiece = compress_piece_bytes(chunk);
+    std::vector<uint8_t> in(kPiece), out(snappy_amd_max_frame_output_ex(kPiece, chunk));
     bool first = true;
     for (;;) {
         const size_t n = read_full(fin, in.data(), in.size());
         if (ferror(fin)) return SNAPPY_AMD_ERR_IO;
         if (n == 0 && !first) break;
         size_t len = 0;
-        int rc = frame_compress_piece(h.ctx(), in.data(), n, first ? 0u : SNAPPY_AMD_FRAME_NO_IDENTIFIER, out.data(),
-                                      out.size(), &len);
+        int rc = frame_compress_piece(h.ctx(), in.data(), n, chunk,
+                                      flags | (first ? 0u : SNAPPY_AMD_FRAME_NO_IDENTIFIER), out.data(), out.size(),
+                                      &len);
         if (rc) return rc;
         if (len && fwrite(out.data(), 1, len, fout) != len) return SNAPPY_AMD_ERR_IO;
         first = false;

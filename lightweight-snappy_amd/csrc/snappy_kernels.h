@@ -45,6 +45,12 @@ __global__ void k2_emit_units(const uint8_t *__restrict__ in, uint64_t n, uint32
                               uint64_t header_value, const uint2 *__restrict__ tokens, uint32_t tok_cap,
                               const uint32_t *__restrict__ ntok, const uint32_t *__restrict__ seg_off, uint32_t segs,
                               const uint64_t *__restrict__ offsets, uint8_t *__restrict__ out);
+// k2_emit_units, but a unit with skip[u] != 0 writes nothing (the framed compressor's stored chunks)
+__global__ void k2_emit_units_sel(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit, uint32_t hdr_mode,
+                                  uint64_t header_value, const uint2 *__restrict__ tokens, uint32_t tok_cap,
+                                  const uint32_t *__restrict__ ntok, const uint32_t *__restrict__ seg_off,
+                                  uint32_t segs, const uint64_t *__restrict__ offsets, uint8_t *__restrict__ out,
+                                  const uint32_t *__restrict__ skip);
 // K2 segments: 256 tokens (4 per lane); waves per unit
 #ifndef SNAPPY_K2_SEG
 #define SNAPPY_K2_SEG 256u

@@ -2225,6 +2225,24 @@ __global__ __launch_bounds__(64, 6) void kr2_emit_lunits(const uint8_t *__restri
     kr2_emit_one(base + rfl64(off) + at, rec, ntok, offsets, out, blk == 0 ? SNAPPY_HDR_FIRST_UNIT : SNAPPY_HDR_NONE,
                  len);
 }
+
+// K2 for a framed call that stores incompressible chunks (snappy_frame.hip): a unit
+// with skip[u] set owns a slot sized for its stored bytes, not for its stream, and
+// writes nothing.  An entry point of its own, behind the others: k2_emit_units keeps
+// its instructions and its place in the object (see snappy_k2_emit.inc).
+__global__ __launch_bounds__(64, 6) void k2_emit_units_sel(const uint8_t *__restrict__ in, uint64_t n, uint32_t unit,
+                                                        uint32_t hdr_mode, uint64_t header_value,
+                                                        const uint2 *__restrict__ tokens, uint32_t tok_cap,
+                                                        const uint32_t *__restrict__ ntok,
+                                                        const uint32_t *__restrict__ seg_off, uint32_t segs,
+                                                        const uint64_t *__restrict__ offsets, uint8_t *__restrict__ out,
+                                                        const uint32_t *__restrict__ skip)
+{
+    if (skip[blockIdx.x]) return;
+#define K2_RECORDS 0
+#include "snappy_k2_emit.inc"
+#undef K2_RECORDS
+}
 #endif
 
 // ---------------------------------------------------------------------------

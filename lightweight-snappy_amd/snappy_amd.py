@@ -38,6 +38,7 @@ ERR_INDEX = -11
 ERR_CHECKSUM = -12
 ERR_DEPENDENT = -13  # range decode: a block of the range needs bytes of an earlier block
 FRAME_NO_IDENTIFIER = 1  # compress_frame_*: this buffer continues a framed stream
+FRAME_STORE = 2  # compress_frame_*: a chunk whose payload is not 1/8 smaller than its bytes is stored (type 01)
 FRAME_IDENTIFIER = bytes.fromhex("ff060000734e61507059")
 CONTAINER_HADOOP = 0  # Hadoop SnappyCodec blocks (.snappy files)
 CONTAINER_XERIAL = 1  # snappy-java SnappyOutputStream chunks
@@ -142,6 +143,12 @@ _SIGS = {
     "snappy_amd_max_frame_output": (_c.c_size_t, [_c.c_size_t]),
     "snappy_amd_compress_frame_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_void_p,
                                                     _c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "snappy_amd_max_frame_output_ex": (_c.c_size_t, [_c.c_size_t, _c.c_uint32]),
+    "snappy_amd_compress_frame_device_ex": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_uint32,
+                                                       _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "snappy_compress_frame_buffer_ex": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_uint32, _c.c_void_p,
+                                                   _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "snappy_compress_file_framed_ex": (_c.c_int, [_c.c_void_p, _c.c_ulonglong, _c.c_uint32, _c.c_uint32, _c.c_void_p]),
     "snappy_amd_frame_index_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
                                                  _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
     "snappy_amd_decompress_frame_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
@@ -391,18 +398,26 @@ def decompress_multi(data, devices) -> bytes:
     return out.raw[: got.value]
 
 
-def max_frame_output(n: int) -> int:
-    return lib().snappy_amd_max_frame_output(n)
+def max_frame_output(n: int, chunk: int = BLOCK) -> int:
+    """Capacity of a framed stream of n bytes in chunks of `chunk` bytes (0: no such chunk size)."""
+    if not 0 <= chunk <= 0xFFFFFFFF:
+        return 0
+    return lib().snappy_amd_max_frame_output_ex(n, chunk)
 
 
-def compress_frame(data) -> bytes:
+def compress_frame(data, chunk: int = BLOCK, store: bool = False) -> bytes:
     """data in the Snappy framing format (framing_format.txt): the stream
-    identifier, then one compressed chunk with its CRC-32C per 65,536 bytes."""
+    identifier, then one chunk with its CRC-32C per `chunk` bytes (1..65,536):
+    compressed, or with store=True stored (type 01) where the compressed payload
+    is not one eighth smaller than the chunk's bytes."""
     p, n, keep = _buf(data)
-    cap = max_frame_output(n)
+    if not 0 < chunk <= BLOCK:
+        raise SnappyError(ERR_ARG, "compress_frame")
+    cap = max_frame_output(n, chunk)
     out = ctypes.create_string_buffer(cap)
     got = ctypes.c_size_t(0)
-    _check(lib().snappy_compress_frame_buffer(p, n, out, cap, ctypes.byref(got)), "compress_frame")
+    _check(lib().snappy_compress_frame_buffer_ex(p, n, chunk, FRAME_STORE if store else 0, out, cap, ctypes.byref(got)),
+           "compress_frame")
     return out.raw[: got.value]
 
 
@@ -800,21 +815,34 @@ class Codec:
                                               ctypes.c_void_p(out.data_ptr())), "crc32c_device")
         return out[:count]
 
-    def compress_frame_ptr(self, d_in: int, n: int, flags: int, d_out: int, d_chunks: int) -> int:
+    def compress_frame_ptr(self, d_in: int, n: int, flags: int, d_out: int, d_chunks: int,
+                           chunk: Optional[int] = None) -> int:
+        """chunk None: compress_frame_device (65,536-byte chunks, FRAME_NO_IDENTIFIER only);
+        else compress_frame_device_ex with that chunk size (FRAME_STORE too)."""
         got = ctypes.c_size_t(0)
-        _check(lib().snappy_amd_compress_frame_device(self._h, ctypes.c_void_p(d_in), n, flags, ctypes.c_void_p(d_out),
-                                                      ctypes.c_void_p(d_chunks), ctypes.byref(got)),
-               "compress_frame_device")
+        if chunk is None:
+            _check(lib().snappy_amd_compress_frame_device(self._h, ctypes.c_void_p(d_in), n, flags,
+                                                          ctypes.c_void_p(d_out), ctypes.c_void_p(d_chunks),
+                                                          ctypes.byref(got)), "compress_frame_device")
+        else:
+            if not 0 <= chunk <= 0xFFFFFFFF:
+                raise SnappyError(ERR_ARG, "compress_frame_device_ex")
+            _check(lib().snappy_amd_compress_frame_device_ex(self._h, ctypes.c_void_p(d_in), n, chunk, flags,
+                                                             ctypes.c_void_p(d_out), ctypes.c_void_p(d_chunks),
+                                                             ctypes.byref(got)), "compress_frame_device_ex")
         return got.value
 
-    def compress_frame_tensor(self, x, flags: int = 0):
-        """x: contiguous uint8 CUDA tensor -> (framed stream tensor, chunk table tensor)."""
+    def compress_frame_tensor(self, x, flags: int = 0, chunk: int = BLOCK):
+        """x: contiguous uint8 CUDA tensor -> (framed stream tensor, chunk table tensor);
+        chunks of `chunk` bytes, flags FRAME_NO_IDENTIFIER | FRAME_STORE."""
         assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        if not 0 < chunk <= BLOCK:
+            raise SnappyError(ERR_ARG, "compress_frame_device_ex")
         n = x.numel()
-        out = torch.empty(max_frame_output(n), dtype=torch.uint8, device=x.device)
-        chunks = torch.empty((n + BLOCK - 1) // BLOCK + 1, dtype=torch.int64, device=x.device)
+        out = torch.empty(max_frame_output(n, chunk), dtype=torch.uint8, device=x.device)
+        chunks = torch.empty((n + chunk - 1) // chunk + 1, dtype=torch.int64, device=x.device)
         self._bind_stream()
-        length = self.compress_frame_ptr(x.data_ptr(), n, flags, out.data_ptr(), chunks.data_ptr())
+        length = self.compress_frame_ptr(x.data_ptr(), n, flags, out.data_ptr(), chunks.data_ptr(), chunk)
         return out[:length], chunks
 
     def frame_index_tensor(self, frame, max_chunks: Optional[int] = None):
